@@ -2,12 +2,15 @@
 """Headline benchmark: video-clips/sec of the Mr. BLIP QVHighlights train step (ViT-g/14 + Q-Former(32) + Flan-T5-XL with
 LoRA, 60 frames, bf16 operands / fp32 accumulate) on N MI355X — forward, backward, gradient all-reduce and AdamW.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one optimizer step over one batch of synthetic clips resident in HBM.  Data-parallel:
 clips are sharded across ranks (weak scaling, --batch-per-gpu clips each), the only exchange is ONE RCCL all-reduce of the
 flat fp32 gradient buffer of the ~19.5 M trainable parameters per step.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step).  --full adds the figures that need extra work
+or runs of their own: the fc1 roofline, the host enqueue time, the HBM-bound side kernels, the CPU baseline and the committed parity note.
 """
 import argparse
 import json
@@ -268,6 +271,26 @@ def parity_note():
         return None
 
 
+DUMP_SAMPLE = 1 << 22   # elements per dumped array (16 MiB of fp32): the trainable buffer of the QVH engine has ~19.5 M
+
+
+def dump_outputs(out_dir, loss, eng):
+    """What a caller of the train step holds after the LAST timed step, as float32 .npy files (about 32 MiB in all):
+    loss.npy [1] (that step's loss), grad.npy (its gradient, the flat fp32 buffer engine.grad) and trainable.npy (the trainable weights after
+    its AdamW update, engine.flat).  Buffers longer than DUMP_SAMPLE are sampled at the same DUMP_SAMPLE positions every run (sorted, from a
+    fixed seed), so two builds given the same arguments can be compared element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = eng.flat.numel()
+    idx = slice(None)
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(eng.flat.device)
+    arrays = {"loss": loss.detach().reshape(1), "grad": eng.grad[idx], "trainable": eng.flat[idx]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -275,9 +298,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="qvh", choices=list(WORKLOADS))
     ap.add_argument("--batch-per-gpu", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-kernels", action="store_true", help="skip the GB/s table of the HBM-bound side kernels")
-    ap.add_argument("--cpu-baseline-c2", action="store_true", help="also time whole QVH clip steps of the CPU oracle (minutes each): one warm-up + --c2-iters timed")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the fc1 roofline (HIP events inside the "
+                    "timed steps + an untimed exclusive ViT pass), the host enqueue time (two untimed steps), the GB/s table of the HBM-bound side "
+                    "kernels, the CPU baseline and the committed parity note")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/*.npy "
+                    "(see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-hbm-kernels", action="store_true", help="--full without the GB/s table of the HBM-bound side kernels")
+    ap.add_argument("--cpu-baseline-c2", action="store_true", help="--full: also time whole QVH clip steps of the CPU oracle (minutes each): one warm-up + --c2-iters timed")
     ap.add_argument("--c2-iters", type=int, default=3, help="timed QVH clip steps of --cpu-baseline-c2 (BASELINE.md §5: >= 3 after one warm-up)")
     ap.add_argument("--vit-chunk", type=int, default=0, help="frames per ViT pass (0 = engine default)")
     ap.add_argument("--no-dropout", action="store_true", help="debug only: the headline number keeps the reference's dropouts on")
@@ -297,6 +325,10 @@ def main():
                     "encodes clip (i + 1) %% 2, so every look-ahead result is consumed under a DIFFERENT key than the one before (the headline passes the "
                     "same tensor every step; the look-ahead hit is keyed on data_ptr / shape / version)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.cpu_baseline_c2 and not args.full:
+        ap.error("--cpu-baseline-c2 is part of --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -417,7 +449,7 @@ def main():
     with torch.cuda.stream(main_stream):
         step_ev[0].record()
         for i_step in range(args.steps):
-            loss = step(record=True)
+            loss = step(record=args.full)
             step_ev[i_step + 1].record()
     launches = (ops.launch_count - launches0) / max(args.steps, 1)
     allocs_timed = eng.ws_allocation_log[allocs0:]
@@ -432,10 +464,12 @@ def main():
         elapsed = t.item()
     loss_v = float(loss.item())
     step_ms = sorted(step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps))
+    if args.dump_outputs and rank == 0:   # before the untimed steps of --full change the weights
+        dump_outputs(args.dump_outputs, loss, eng)
     # host time to ENQUEUE one step, outside the timed region: inside it the host runs ahead of the GPU until the stream's queue is full
     # and is then throttled to the GPU's pace, so a wall-clock bracket there reads the GPU time.  Two untimed steps, each started on an
     # idle GPU (every rank takes them: the gradient exchange is collective).
-    for _ in range(2):
+    for _ in range(2 if args.full else 0):
         torch.cuda.synchronize()
         with torch.cuda.stream(main_stream):
             step(record="host")
@@ -443,7 +477,7 @@ def main():
     # outside the timed region: the same kernel with the GPU to itself (one plain ViT pass on the main stream) — with the look-ahead
     # the timed launches share the CUs with the previous clip's decoder / encoder-backward kernels
     excl = []
-    if rank == 0 and not args.no_lookahead:
+    if args.full and rank == 0 and not args.no_lookahead:
         eng.probe = excl
         eng.vit_forward(video.reshape(-1, 3, 224, 224), slot=2)
         eng.probe = None
@@ -513,24 +547,25 @@ def main():
                        "t5_encoder_4wave": {"qkv_forward_tile": int(eng.enc_qkv_w4) if (eng.enc_qkv_wc is not None and B * layout.S >= 1024) else 0,
                                             "ksplit_input_gradients": bool(eng._enc_bwd_w4_ok(B * layout.S))}},
             "launches_per_step": round(launches, 1),     # C-ABI kernel launches per step (torch-native ones: ~10, profiles/r02_native_in_step.txt)
-            "host_enqueue_ms": round(1e3 * min(host_s), 2) if host_s else None,   # host time to enqueue one step onto an idle GPU (untimed extra steps); must stay below ms_per_step
+            # --full only (None otherwise): host time to enqueue one step onto an idle GPU (untimed extra steps); must stay below ms_per_step
+            "host_enqueue_ms": round(1e3 * min(host_s), 2) if host_s else None,
             "workspace_allocations_in_timed_region": [n for n, _ in allocs_timed],
             "step_tflop_per_clip": round(step_tf, 3),
             "step_mfu": round(clips_s * step_tf / (world * PEAK_BF16_TFLOPS), 4),   # (frame-shard mode: algorithmic FLOPs of ONE clip; the replicated T5 work is not counted twice)
             "loss": round(loss_v, 4),
             # tiles of a GEMM whose bounded wait for the launch's own thin-role workgroups ran out (csrc/gemm.hip th_err): must be 0
             "thin_role_timeouts": ops.gemm_thin_timeouts(),
-            "roofline": roof,
+            "roofline": roof,   # --full only (None otherwise)
         }
-        note = parity_note()
+        note = parity_note() if args.full else None
         if note is not None:
             out["parity_note"] = note
         if selftest is not None:
             out["collective_selftest"] = selftest   # {"backend": "nccl" (= RCCL), "ranks": N, "ok": true, "allreduce_ms": ...}
             out["rccl_ranks"] = selftest["ranks"] if selftest.get("backend") == "nccl" else 0
-        if world == 1 and not args.no_hbm_kernels:
+        if args.full and world == 1 and not args.no_hbm_kernels:
             out["hbm_kernels"] = {"peak_GBps": PEAK_HBM_GBPS, "unit": "GB/s", "rows": hbm_kernel_report(eng, video, layout)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(full_c2=args.cpu_baseline_c2, c2_iters=args.c2_iters)
         print(json.dumps(out), flush=True)
     if world > 1:

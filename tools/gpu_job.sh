@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 job=$1; shift
 mkdir -p gpurun_out
-B="timeout 600 python bench.py --no-cpu-baseline --no-hbm-kernels"
+B="timeout 600 python bench.py --full --no-cpu-baseline --no-hbm-kernels"
 case "$job" in
   tests)        # the whole -m gpu suite (+ the measured-error log) ; args: extra pytest args
     timeout 1500 python -m pytest tests -m gpu -q -x "$@" 2>&1 | tail -15 | tee gpurun_out/tests.log ;;

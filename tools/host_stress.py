@@ -18,7 +18,7 @@ share = max(1, ncpu // 8)
 procs = []
 for i in range(N):
     cores = f"{i * share}-{(i + 1) * share - 1}"
-    cmd = ["taskset", "-c", cores, sys.executable, os.path.join(ROOT, "bench.py"), "--workload", WL, "--steps", "12", "--warmup", "4", "--no-cpu-baseline",
+    cmd = ["taskset", "-c", cores, sys.executable, os.path.join(ROOT, "bench.py"), "--workload", WL, "--steps", "12", "--warmup", "4", "--full", "--no-cpu-baseline",
            "--no-hbm-kernels", "--graph", GRAPH]
     procs.append((cores, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)))
 print(f"# {N} concurrent bench.py --workload {WL} --graph {GRAPH} processes on one GPU, each pinned to {share} of {ncpu} cores (1/8 of the box)")

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 run() { local name=$1; shift
-  env "$@" python bench.py --steps 25 --warmup 8 --no-cpu-baseline --no-hbm-kernels 2>>$O/r06_ab7_err.log | python tools/bench_brief.py | sed "s/^/$name: /"; }
+  env "$@" python bench.py --full --steps 25 --warmup 8 --no-cpu-baseline --no-hbm-kernels 2>>$O/r06_ab7_err.log | python tools/bench_brief.py | sed "s/^/$name: /"; }
 {
 run default X=1
 run sched14:64,39:32 MRB_VIT_RESERVE_SCHED=14:64,39:32

@@ -11,8 +11,8 @@ if [ "$1" != "notests" ]; then
 timeout 2400 python -m pytest tests -m gpu -q --tb=short 2>&1 | grep -E "^E |passed|failed|^FAILED|^tests/.*(Error|assert)" | head -60 | tee $O/${T}_tests.log
 cp profiles/r06_parity_errors.json $O/${T}_parity_errors.json 2>/dev/null
 fi
-python bench.py > $O/${T}_bench_qvh.json 2>> $E
-python bench.py --workload charades --steps 30 --warmup 8 --no-cpu-baseline --no-hbm-kernels > $O/${T}_bench_charades.json 2>> $E
+python bench.py --full > $O/${T}_bench_qvh.json 2>> $E
+python bench.py --full --workload charades --steps 30 --warmup 8 --no-cpu-baseline --no-hbm-kernels > $O/${T}_bench_charades.json 2>> $E
 for f in qvh charades; do python tools/bench_brief.py < $O/${T}_bench_$f.json; done | tee $O/${T}_brief.txt
 python tools/phase_times2.py > $O/${T}_phase_times.txt 2>> $E
 python tools/phase_times2.py --no-lookahead >> $O/${T}_phase_times.txt 2>> $E

@@ -7,13 +7,13 @@ R=$PWD; O=$R/gpurun_out; mkdir -p $O
 export GRAFT_REPO_ROOT=$R
 E=$O/r06_final_err.log; : > $E
 timeout 2400 python -m pytest tests -m gpu -q --tb=short 2>&1 | grep -E "^E |passed|failed|^FAILED|^tests/.*(Error|assert)" | head -60 | tee $O/r06_final_tests.log
-python bench.py > $O/r06_final_bench_qvh.json 2>> $E
-python bench.py --workload charades --steps 30 --warmup 8 --no-cpu-baseline --no-hbm-kernels > $O/r06_final_bench_charades.json 2>> $E
-python bench.py --workload anet --steps 12 --warmup 4 --no-cpu-baseline --no-hbm-kernels > $O/r06_final_bench_anet.json 2>> $E
-python bench.py --batch-per-gpu 4 --steps 8 --warmup 3 --no-cpu-baseline --no-hbm-kernels > $O/r06_final_bench_qvh_b4.json 2>> $E
-python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-hbm-kernels --no-lookahead > $O/r06_final_bench_qvh_nolookahead.json 2>> $E
-python bench.py --steps 24 --warmup 8 --no-cpu-baseline --no-hbm-kernels --vary-text > $O/r06_final_bench_qvh_varytext.json 2>> $E
-python bench.py --steps 24 --warmup 8 --no-cpu-baseline --no-hbm-kernels --vary-video > $O/r06_final_bench_qvh_varyvideo.json 2>> $E
+python bench.py --full > $O/r06_final_bench_qvh.json 2>> $E
+python bench.py --full --workload charades --steps 30 --warmup 8 --no-cpu-baseline --no-hbm-kernels > $O/r06_final_bench_charades.json 2>> $E
+python bench.py --full --workload anet --steps 12 --warmup 4 --no-cpu-baseline --no-hbm-kernels > $O/r06_final_bench_anet.json 2>> $E
+python bench.py --full --batch-per-gpu 4 --steps 8 --warmup 3 --no-cpu-baseline --no-hbm-kernels > $O/r06_final_bench_qvh_b4.json 2>> $E
+python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-hbm-kernels --no-lookahead > $O/r06_final_bench_qvh_nolookahead.json 2>> $E
+python bench.py --full --steps 24 --warmup 8 --no-cpu-baseline --no-hbm-kernels --vary-text > $O/r06_final_bench_qvh_varytext.json 2>> $E
+python bench.py --full --steps 24 --warmup 8 --no-cpu-baseline --no-hbm-kernels --vary-video > $O/r06_final_bench_qvh_varyvideo.json 2>> $E
 for f in qvh charades anet qvh_b4 qvh_nolookahead qvh_varytext qvh_varyvideo; do python tools/bench_brief.py < $O/r06_final_bench_$f.json; done | tee $O/r06_final_brief.txt
 python tools/phase_times2.py > $O/r06_final_phase_times.txt 2>> $E
 python tools/phase_times2.py --no-lookahead >> $O/r06_final_phase_times.txt 2>> $E
