@@ -286,10 +286,10 @@ int mrblip_gemm_clear_one_shots(void);
  *  - tout0..2 (bf16 output, plain or bias epilogue, heads of 64): head-transposed copies of up to three consecutive column ranges of width
  *    t_inner — exactly what mrblip_head_transpose would write from the output ([B, H, 64, t_spad], rows b * t_rows + s, pad columns zeroed;
  *    one clip, or t_rows %% 32 == 0): q / k / v of a fused projection reach the attention kernels without a transpose launch
- *    (modeling_t5.py:536-560, Qformer.py:141-147 feeding :195-262);
+ *    (modeling_t5.py:536-560, Qformer.py:141-147 feeding :195-262)
+ *    (t_count > 0: range j < t_count goes to tout0 + j * t_stride elements instead of the three pointers);
  *  - ext_group_n > 0: output columns [g * ext_group_n, (g + 1) * ext_group_n) take columns [64 g, 64 g + 64) of Aext as their K extension:
  *    the cross-attention K / V projections of ALL decoder layers (modeling_t5.py:561-599, peft LoRA on each) as one GEMM. */
- *    (t_count > 0: range j < t_count goes to tout0 + j * t_stride elements instead of the three pointers);
 int mrblip_gemm_set_extra(void* tout0, void* tout1, void* tout2, int t_inner, int t_rows, int t_spad, long long t_bs, long long t_hs,
                           long long t_stride, int t_count, int ext_group_n);
 /* Launch shape of mrblip_dec_proj for R <= 16 (round 4; host-side state, no torch counterpart): n_blocks > 0 = blocks of the streaming kernel for

@@ -14,6 +14,8 @@
 // accumulator group -> 16-B (fp32) / 8-B (bf16) row-major stores.
 #include "common.h"
 #include "lora_thin.h"
+#include "../../include/mrblip_hip.h"
+#include <stddef.h>
 #include <type_traits>
 // TILE_PIPE (experiment, off): 1 = fragments of k-step kk+1 requested before the MFMAs of kk AND the next stage's LDS-DMA pieces spread over
 // the k-steps (64x128 tile, K = 10240: 129.7 us against 107.3 us — pieces issued later land later, the 2-stage ring waits for them);
@@ -2678,13 +2680,11 @@ extern "C" int mrblip_lora_tn(const void* Y, long long ldy, const void* U, long 
 
 // The weight-gradient pairs of SEVERAL fused groups in ONE launch (round 5): jobs[i] is what one mrblip_lora_grads call took (same
 // arithmetic, same block -> output ownership, so the same bits); at most 8 jobs (16 problems).
-struct MrblipLoraGradsJob {   // (= the typedef of include/mrblip_hip.h)
-  const void* dY; long long lddy; const void* U; long long ldu; const void* X; long long ldx; const void* G; long long ldg;
-  int M, N, K, R;
-  float* dBt[4]; int b_col0[4]; int b_ncols[4]; long long b_lds[4];
-  float* dA[4]; long long a_lds[4];
-  uint32_t site; float p_drop;
-};
+// MrblipLoraGradsJob is the public typedef (include/mrblip_hip.h); ops.LoraGradsJob mirrors this layout in ctypes
+// (tests/test_abi_cpu.py compiles the header and compares both)
+static_assert(sizeof(MrblipLoraGradsJob) == 248 && offsetof(MrblipLoraGradsJob, dBt) == 80 && offsetof(MrblipLoraGradsJob, dA) == 176 &&
+                  offsetof(MrblipLoraGradsJob, a_lds) == 208 && offsetof(MrblipLoraGradsJob, site) == 240 && offsetof(MrblipLoraGradsJob, p_drop) == 244,
+              "MrblipLoraGradsJob: the C ABI layout changed (update ops.LoraGradsJob with it)");
 extern "C" int mrblip_lora_grads_batched(int n_jobs, const MrblipLoraGradsJob* jobs, const uint32_t* seed_ptr, hipStream_t stream) {
   MRB_REQUIRE(n_jobs > 0 && 2 * n_jobs <= TN_MAX_PROBLEMS && jobs, "lora_grads_batched: 1..%d jobs", TN_MAX_PROBLEMS / 2);
   TnMulti q = {};

@@ -31,6 +31,8 @@
 // accumulation, fp32 two-pass LayerNorm, erf-GELU of common.h) and the same dropout draws (element dropout: mrb_keep4 on row * 768 + n;
 // probability dropout: draws v3, attention.hip) — outputs agree with the chain to fp32 summation order (tests/test_qformer_fused_gpu.py).
 #include "common.h"
+#include "../../include/mrblip_hip.h"
+#include <stddef.h>
 
 struct QfLayerArgs {   // kernel-side form of mrblip_qformer_layer (include/mrblip_hip.h)
   const bf16_t *qkv_w, *so_w, *cq_w, *co_w, *i_w, *o_w;            // bf16 [N, K] row-major (ld = K): 2304x768, 768x768, 768x768, 768x768, 3072x768, 768x3072
@@ -592,28 +594,11 @@ __global__ __launch_bounds__(256, 1) void qformer_layer_fwd_kernel(const QfLayer
   }
 }
 
-// the public argument block (include/mrblip_hip.h: mrblip_qformer_layer) — plain pointers and sizes
-struct mrblip_qformer_layer {
-  const void *qkv_w, *so_w, *cq_w, *co_w, *i_w, *o_w;
-  const float *qkv_b, *so_b, *s_lnw, *s_lnb, *cq_b, *co_b, *c_lnw, *c_lnb, *i_b, *o_b, *o_lnw, *o_lnb;
-  const float* x_in;
-  float* x_out;
-  void* xb_out;
-  long long ldxb;
-  void *qkv, *o;
-  long long ldo;
-  float *lse, *y;
-  void *qc, *oc;
-  float *lsec, *y2;
-  const void *kv, *vt;
-  void* hpre;
-  float* y3;
-  int F, Tv, Tvp, has_cross;
-  const uint32_t* seed_ptr;
-  float p_drop;
-  uint32_t site_sattn, site_so, site_cattn, site_co, site_ffn;
-  float eps;
-};
+// the public argument block is mrblip_qformer_layer of include/mrblip_hip.h — plain pointers and sizes; ops.QformerLayer mirrors this
+// layout in ctypes (tests/test_abi_cpu.py compiles the header and compares both)
+static_assert(sizeof(mrblip_qformer_layer) == 336 && offsetof(mrblip_qformer_layer, ldxb) == 168 && offsetof(mrblip_qformer_layer, y3) == 272 &&
+                  offsetof(mrblip_qformer_layer, F) == 280 && offsetof(mrblip_qformer_layer, seed_ptr) == 296 && offsetof(mrblip_qformer_layer, eps) == 328,
+              "mrblip_qformer_layer: the C ABI layout changed (update ops.QformerLayer with it)");
 
 static DropoutArg qf_drop(const uint32_t* seed_ptr, uint32_t site, float p) {
   DropoutArg d;

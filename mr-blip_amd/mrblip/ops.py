@@ -478,14 +478,15 @@ def lora_pack(flat, acat, wext, bblk, acatt, desc, n_adapters, scale=1.0):
     _chk(_lora_pack(_p(flat), _p(acat), _p(wext), _p(bblk), _p(acatt), _p(desc), n_adapters, scale, _stream()))
 
 
-def lora_grads(dy, u, x, g, dBt, b_col0, b_ncols, dA, K, drop: Optional[Dropout] = None):
-    """both weight gradients of a fused LoRA group in one launch: dBt[j] += u_j^T dy[:, cols_j], dA[j] += g_j^T dropout(x[:, :K])"""
+def lora_grads(dy, u, x, g, dBt, b_col0, b_ncols, dA, K, drop: Optional[Dropout] = None, b_lds=None, a_lds=None):
+    """both weight gradients of a fused LoRA group in one launch: dBt[j] += u_j^T dy[:, cols_j], dA[j] += g_j^T dropout(x[:, :K]).
+    b_lds / a_lds: row pitches (elements) of the outputs, default b_ncols / K (contiguous [8, cols] tensors)"""
     M, N = dy.shape
     n = len(dBt)
     sp, site, p = _d(drop)
     _chk(_lora_grads(_p(dy), _ld(dy), _p(u), _ld(u), _p(x), _ld(x), _p(g), _ld(g), M, N, K, 8 * n,
-                     (vp * n)(*[o.data_ptr() for o in dBt]), (i32 * n)(*b_col0), (i32 * n)(*b_ncols), (ll * n)(*b_ncols),
-                     (vp * n)(*[o.data_ptr() for o in dA]), (ll * n)(*([K] * n)), sp, site, p, _stream()))
+                     (vp * n)(*[o.data_ptr() for o in dBt]), (i32 * n)(*b_col0), (i32 * n)(*b_ncols), (ll * n)(*(b_lds or b_ncols)),
+                     (vp * n)(*[o.data_ptr() for o in dA]), (ll * n)(*(a_lds or [K] * n)), sp, site, p, _stream()))
 
 
 class LoraGradsJob(C.Structure):
@@ -496,14 +497,14 @@ class LoraGradsJob(C.Structure):
                 ("dA", vp * 4), ("a_lds", ll * 4), ("site", u32), ("p_drop", f32)]
 
 
-def lora_grads_job(dy, u, x, g, dBt, b_col0, b_ncols, dA, K, drop: Optional[Dropout] = None):
+def lora_grads_job(dy, u, x, g, dBt, b_col0, b_ncols, dA, K, drop: Optional[Dropout] = None, b_lds=None, a_lds=None):
     """the arguments of one ``lora_grads`` call as a job of ``lora_grads_batched`` (a tuple: (seed tensor or None, filled struct))"""
     j = LoraGradsJob()
     j.dY, j.lddy, j.U, j.ldu, j.X, j.ldx, j.G, j.ldg = dy.data_ptr(), _ld(dy), u.data_ptr(), _ld(u), x.data_ptr(), _ld(x), g.data_ptr(), _ld(g)
     j.M, j.N, j.K, j.R = dy.shape[0], dy.shape[1], K, 8 * len(dBt)
     for i in range(len(dBt)):
-        j.dBt[i], j.b_col0[i], j.b_ncols[i], j.b_lds[i] = dBt[i].data_ptr(), b_col0[i], b_ncols[i], b_ncols[i]
-        j.dA[i], j.a_lds[i] = dA[i].data_ptr(), K
+        j.dBt[i], j.b_col0[i], j.b_ncols[i], j.b_lds[i] = dBt[i].data_ptr(), b_col0[i], b_ncols[i], (b_lds or b_ncols)[i]
+        j.dA[i], j.a_lds[i] = dA[i].data_ptr(), (a_lds or [K] * len(dBt))[i]
     seed = None
     if drop is not None and drop.p > 0.0:
         j.site, j.p_drop, seed = drop.site, drop.p, drop.seed
@@ -513,10 +514,10 @@ def lora_grads_job(dy, u, x, g, dBt, b_col0, b_ncols, dA, K, drop: Optional[Drop
 def lora_grads_batched(jobs):
     """both weight gradients of up to 8 fused LoRA groups in ONE launch (same bits as one ``lora_grads`` call per group)"""
     n = len(jobs)
-    assert 1 <= n <= 8
     seeds = {s.data_ptr(): s for s, _ in jobs if s is not None}
-    assert len(seeds) <= 1, "one device seed per launch"
-    arr = (LoraGradsJob * n)(*[j for _, j in jobs])
+    if len(seeds) > 1:
+        raise MrblipError("lora_grads_batched: one device seed per launch, got %d" % len(seeds))
+    arr = (LoraGradsJob * max(n, 1))(*[j for _, j in jobs])   # (0 or more than 8 jobs: the library refuses them before any launch)
     sp = next(iter(seeds)) if seeds else None
     _chk(_lora_grads_b(arr, n, sp, _stream()))
 

@@ -13,14 +13,14 @@ pytestmark = pytest.mark.gpu
 from util import check, relerr  # noqa: E402
 
 
-def _step(flags, B=1, steps=2):
+def _step(flags, B=1, steps=2, dec_layers=3):
     import bench
     from mrblip import prompt as P
     from mrblip.engine import EngineConfig, MrBlipEngine, RandomSource
     from mrblip.tokenizer import FixtureTokenizer
     dev = torch.device("cuda:0")
     cfg = EngineConfig(vit_dim=320, vit_depth=2, vit_heads=5, vit_mlp=512, qf_dim=256, qf_heads=4, qf_inter=512, qf_layers=4, num_query=32,
-                       d_model=256, d_kv=64, t5_heads=4, d_ff=512, t5_layers=3, t5_dec_layers=3)
+                       d_model=256, d_kv=64, t5_heads=4, d_ff=512, t5_layers=3, t5_dec_layers=dec_layers)
     eng = MrBlipEngine(cfg, RandomSource(dev, seed=77), dev, lora_init=bench.lora_init_nonzero, seed=11)
     flags = dict(dict(enc_qkv_w4=0, enc_bwd_w4=False), **flags)     # the round-4 paths under test live in the generic tile; the 4-wave forms have their own tests below
     for k, v in flags.items():
@@ -64,6 +64,36 @@ def test_gemm_epilogue_transposes_and_stacked_cross_kv_equal_the_launches_they_r
     _step(dict(), steps=1)
     launches_new = ops.launch_count - n0
     assert launches_new < launches_old - 3 * 10, (launches_old, launches_new)     # 3 + 3 layers: transposes and per-layer K / V launches are gone
+
+
+def test_batched_lora_weight_gradients_are_bit_identical_to_one_launch_per_group():
+    """lora_grads_batch (MRB_LORA_GRADS_BATCH) is documented as an A/B switch with the same bits: the batched launch runs the two-tile
+    body (CT = 2) where the per-group launches run the one-tile body, so loss and the whole flat gradient are compared bitwise"""
+    l0, g0, eng0, _ = _step(dict(lora_grads_batch=False))
+    l1, g1, eng1, _ = _step(dict(lora_grads_batch=True))
+    assert not eng0.lora_grads_batch and eng1.lora_grads_batch and eng1.grad_side_stream_enabled
+    assert l1 == l0, (l1, l0)
+    assert torch.equal(g1, g0), relerr(g1, g0)
+
+
+@pytest.mark.parametrize("fwd_chunks,bwd_chunks", [((5, 7), (12,)), ((12,), (4, 8))])
+def test_stacked_cross_kv_in_chunks_of_four_and_more_layers(fwd_chunks, bwd_chunks):
+    """12 decoder layers, the stacked cross K / V path in chunks of 4..12 layers (production runs 2 / 6 / 8 / 8 forward and 10 / 8 / 4 / 2
+    backward with 24 layers; the 3-layer engine above never gets past 3): every cross-attention K / V adapter's weight gradients against the
+    per-layer path, tensor by tensor"""
+    l0, g0, eng0, _ = _step(dict(cross_kv_batched=False), dec_layers=12)
+    l1, g1, eng1, _ = _step(dict(ckv_fwd_chunks=fwd_chunks, ckv_bwd_chunks=bwd_chunks), dec_layers=12)
+    assert eng1.ckv_all is not None and eng1.ckv_all["L"] == 12
+    tag = "round-4 paths, 12 decoder layers, cross K/V chunks %s / %s: " % (",".join(map(str, fwd_chunks)), ",".join(map(str, bwd_chunks)))
+    check(tag + "loss (rel)", max(abs(a - b) / abs(b) for a, b in zip(l1, l0)), 1.5e-7)    # (measured 0: the forward is the same arithmetic)
+    eb = ea = 0.0
+    for L0, L1 in zip(eng0.t5["dec"], eng1.t5["dec"]):
+        for a0, a1 in zip(L0["ckv"].adapters, L1["ckv"].adapters):
+            assert a1.dA.abs().sum() > 0 and a1.dBt.abs().sum() > 0
+            eb, ea = max(eb, relerr(a1.dBt, a0.dBt)), max(ea, relerr(a1.dA, a0.dA))
+    check(tag + "cross K/V dB^T, worst adapter", eb, 1.5e-7)     # (measured 0)
+    check(tag + "cross K/V dA, worst adapter", ea, 1.5e-7)       # (measured 0)
+    check(tag + "flat gradient", relerr(g1, g0), 6.5e-4)   # (measured 3.1e-4: the encoder-output gradient is summed in another fp32 order, see above)
 
 
 def test_several_clips_whose_length_is_not_a_multiple_of_32_fall_back():
