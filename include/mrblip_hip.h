@@ -373,6 +373,42 @@ typedef struct mrblip_qformer_layer {
 } mrblip_qformer_layer;
 int mrblip_qformer_layer_fwd(const mrblip_qformer_layer* layer, mrblip_stream_t stream);
 
+/* Device-resident beam search of generate (csrc/search.hip): mrblip/search.py beam_search — HF's beam search as the reference calls it,
+ * blip2_mr.py:883-899 — with every piece of state in device memory, so that no decoding step waits for the host.  Candidate order
+ * everywhere: higher score first, EQUAL scores by lower flat index (beam * V + token); pool entries: equal scores by lower slot.  No float
+ * atomics: two runs give the same bits.  int tensors are int32; sequence rows (seq_*, pool_seq) have a leading dimension lds >=
+ * max_new_tokens + 1 and start with the start token.
+ *
+ * mrblip_beam_topk (search.py:124-131): for each of the R / K clips the 2K best of
+ *   log_softmax(logits)[row, v] (x repetition_penalty — HF's processor on the log-probabilities: lp < 0 ? lp * p : lp / p — for every v among
+ *   the row's first cur_len sequence tokens; -inf for v == eos_id while cur_len < min_length) + beam_scores[row]
+ * over the clip's K * V candidates, best first: cand_score / cand_index [R / K, 2K].  logits fp32 [R, V], ld = ldl (what the decoder's LM
+ * head leaves).  K in 1..16, V >= 2K, R % K == 0, V <= 131072 — rejected before any launch otherwise.  The vocabulary is split over
+ * NS = ceil(V / 2048) workgroups per row (max / sum-exp partials, then the chunk's 2K best); a last launch merges the clip's K * NS sorted
+ * lists in a fixed order.  ws: caller-owned scratch of >= 4 * R * NS * (2 + 4K) bytes, 16-byte aligned, no initial state needed. */
+int mrblip_beam_topk(const float* logits, long long ldl, const float* beam_scores, const int* seqs, long long lds, int R, int K, int V,
+                     int cur_len, int min_length, int eos_id, float repetition_penalty, float* cand_score, int* cand_index, void* ws,
+                     long long ws_bytes, mrblip_stream_t stream);
+/* search.py:134-160 on the device state, one small workgroup per clip: walks the 2K candidates in order; an EOS candidate of rank < K enters
+ * the clip's pool of K finished hypotheses (pool_score / pool_len [B, K], pool_seq [B, K, lds], pool_n [B]; score = sum / len_pow; the worst
+ * entry is evicted when the newcomer is better), the first K other candidates become the beams: seq_out rows (gathered from their parent
+ * rows of seq_in — the two halves of a ping-pong buffer), beam_scores, parents [R] (row of the previous step each row extends) and tokens
+ * [R] (newest token of each row).  Then the `done` rule (search.py:157-159): pool full and its worst >= best candidate / len_pow -> done[b]
+ * = 1, *done_count += 1.  A clip already done keeps its rows, appends pad_id, gets scores 0 and identity parents; nothing else of it changes.
+ * len_pow = cur_len ** length_penalty, computed by the caller in double. */
+int mrblip_beam_advance(const float* cand_score, const int* cand_index, const int* seq_in, int* seq_out, long long lds, float* beam_scores,
+                        int* parents, int* tokens, float* pool_score, int* pool_len, int* pool_seq, int* pool_n, int* done, int* done_count,
+                        int B, int K, int V, int cur_len, int eos_id, int pad_id, float len_pow, mrblip_stream_t stream);
+/* search.py:164-170: the running beams (length cur_len, score / len_pow with len_pow = (cur_len - 1) ** length_penalty) of clips that are
+ * not done join their pool; every pool is ranked and its num_return best leave in out [B, num_return, lds + 2] int32 rows of
+ * {length, score (fp32 bits), tokens...}.  Call once per search: it updates the pools. */
+int mrblip_beam_finalize(const int* seq, long long lds, const float* beam_scores, float* pool_score, int* pool_len, int* pool_seq, int* pool_n,
+                         const int* done, int B, int K, int cur_len, float len_pow, int num_return, int* out, mrblip_stream_t stream);
+/* dst[p, r, :t, :] = src[p, parents[r], :t, :] for bf16 caches [planes, R, Lmax, inner] (the decoder's self-attention K / V cache
+ * [2, layers, R, Lmax, inner] with planes = 2 * layers), parents read on the device: HF's _reorder_cache(beam_idx) without the host
+ * (search.py:94-97).  src != dst, because parents repeat.  inner % 8 == 0; an index outside 0..R-1 copies the row itself. */
+int mrblip_kv_gather_rows(const void* src, void* dst, const int* parents, int planes, int R, int Lmax, int inner, int t, mrblip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

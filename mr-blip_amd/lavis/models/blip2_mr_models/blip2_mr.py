@@ -307,6 +307,7 @@ class BLIP2_MR(BaseModel):
             weights=weights, synthetic_weights=cfg.get("synthetic_weights", False),
             seed=cfg.get("seed", None),  # None: the engine's dropout stream follows torch's seed = run.seed + rank (train.py setup_seeds)
         )
+        model.generate_device_search = bool(cfg.get("generate_device_search", False))
         model.load_checkpoint_from_config(cfg)
         return model
 
@@ -332,6 +333,14 @@ class BLIP2_MR(BaseModel):
     _reserved = False    # engine workspaces sized for the longest step (first forward)
     generate_cross_cache = True  # project the decoder's cross-attention K/V once per clip (False: per step and beam, for the A/B test)
     generate_self_cache = True   # self-attention K/V cache: one new position per decoding step (False: re-run the prefix, for the A/B test)
+    # beam search with its state in device memory (mrblip.search.DeviceBeamSearch): no log_softmax launch, no .cpu() and no upload per
+    # decoding step.  Opt-in (model config key of the same name); taken for beam searches of <= 16 beams with both caches on and
+    # max_length < 128, every other call runs the host search as before.
+    generate_device_search = False
+    generate_poll_done = True    # device search: poll the done counter (two steps late) and stop early; False runs all max_length steps
+    generate_trace = None        # a list: receives the HOST beam search's decision trace (search.beam_search's ``trace``), for tests
+    generate_detail = None       # a list: receives the host search's ``detail`` (candidate indices, next score, score magnitude)
+    last_generate_stats = None   # device search: {"steps", "steps_after_done", "search_host_s"} of the last generate call
 
     def forward(self, samples):
         """samples: the reference's dict (blip2_mr.py:433-445).  Optional extra key ``next_video``: the NEXT batch's frames (the train
@@ -559,7 +568,12 @@ class BLIP2_MR(BaseModel):
             # function re-runs the short decoder prefix on the HIP decoder (weight-streaming bound: <= 64 rows cost what one row costs)
             from mrblip.search import beam_search
 
-            if cross is not None and self.generate_self_cache and int(max_length) < 128:
+            self.last_generate_stats, best = None, None
+            if (self.generate_device_search and not use_nucleus_sampling and not greedy_pen and K <= 16 and cross is not None
+                    and self.generate_self_cache and int(max_length) < 128):
+                best = self._device_beam_search(B, K, int(max_length), int(min_length), float(length_penalty), float(repetition_penalty), n_ret,
+                                                cross, mask_k)
+            elif cross is not None and self.generate_self_cache and int(max_length) < 128:
                 # incremental decoding (HF use_cache=True): one new position per step against the self-attention K/V cache, which the
                 # search re-orders through `parents` (HF's _reorder_cache)
                 state = eng.t5_decode_begin(B * K, int(max_length) + 1)
@@ -577,14 +591,17 @@ class BLIP2_MR(BaseModel):
                     last = logits.view(B * K, Ld, -1)[:, -1].float()
                     return last.cpu() if raw_logits else torch.log_softmax(last, -1).cpu()
 
-            if use_nucleus_sampling or greedy_pen:
+            if best is not None:
+                pass                                                  # (the device search has run)
+            elif use_nucleus_sampling or greedy_pen:
                 from mrblip.search import sample_search
                 best = sample_search(step_fn, B, n_ret, int(max_length), min_length=int(min_length), top_p=float(top_p), temperature=float(temperature),
                                      repetition_penalty=float(repetition_penalty), eos_id=1, pad_id=0, start_id=0,
                                      generator=getattr(self, "sampling_generator", None), greedy=greedy_pen)
             else:
                 best = beam_search(step_fn, B, K, int(max_length), min_length=int(min_length), length_penalty=float(length_penalty),
-                                   eos_id=1, pad_id=0, start_id=0, repetition_penalty=float(repetition_penalty), num_return=n_ret)
+                                   eos_id=1, pad_id=0, start_id=0, repetition_penalty=float(repetition_penalty), num_return=n_ret,
+                                   trace=self.generate_trace, detail=self.generate_detail)
             self.last_sequences = [seq.clone() for seq in best]   # token ids of the winning hypotheses (start token first): parity tests
             out_text = [self.t5_tokenizer.decode(seq[1:], skip_special_tokens=True) for seq in best]
             raw = list(out_text)
@@ -594,6 +611,34 @@ class BLIP2_MR(BaseModel):
                     "answer": samples.get("relevant_windows", [""] * B), "qid": samples.get("query_id", [str(i) for i in range(B)])}
         finally:
             eng.training = was_training
+
+    def _device_beam_search(self, B, K, max_length, min_length, length_penalty, repetition_penalty, n_ret, cross, mask):
+        """generate's decoding loop with the search on the device: every step is t5_decode_step on the search's device tokens / parents
+        followed by search.step on the raw logits — the host only enqueues.  Early stop: after every step the done counter is copied to
+        a pinned slot behind an event; before step t is enqueued the event of step t - 2 is QUERIED and the loop ends when its slot
+        says that all B clips are done.  The one blocking transfer is the output block of finalize."""
+        from mrblip.search import DeviceBeamSearch
+        eng = self.engine
+        key = (B, K, max_length, min_length, length_penalty, repetition_penalty, n_ret)
+        search = self._dev_search[1] if self._dev_search is not None and self._dev_search[0] == key else None
+        if search is None:   # (state lives in the engine's named workspaces: one search object at a time)
+            search = DeviceBeamSearch(B, K, max_length, min_length=min_length, length_penalty=length_penalty, eos_id=1, pad_id=0, start_id=0,
+                                      repetition_penalty=repetition_penalty, num_return=n_ret, device=eng.dev, buf=eng.buf)
+            self._dev_search = (key, search)
+        else:
+            search.reset()
+        state = eng.t5_decode_begin(B * K, max_length + 1, alt_cache=True)
+        for _ in range(max_length):
+            if self.generate_poll_done and search.finished():
+                break
+            logits = eng.t5_decode_step(state, search.tokens, search.parents, cross, B, mask)
+            search.step(logits)
+            search.done_count_async()
+        best = search.finalize()
+        self.last_generate_stats = {"steps": search.steps, "steps_after_done": search.steps_after_done(), "search_host_s": search.host_seconds}
+        return best
+
+    _dev_search = None
 
     # ------------------------------------------------------------------ checkpoints: trainable tensors only, reference key names
     def state_dict(self, *args, **kwargs):

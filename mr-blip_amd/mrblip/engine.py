@@ -1941,9 +1941,11 @@ class MrBlipEngine:
 
     # ---- incremental decoding (generate): self-attention K / V cache, one new position per call
     @torch.no_grad()
-    def t5_decode_begin(self, R: int, max_len: int) -> dict:
+    def t5_decode_begin(self, R: int, max_len: int, alt_cache: bool = False) -> dict:
         """State of an incremental decode of R sequences (beams x clips) of at most ``max_len`` positions: the self-attention keys and
-        values of every decoder layer, row-major like the qkv buffer they are cut from: [2 (k, v), layers, R, Lmax, H * d_kv] bf16."""
+        values of every decoder layer, row-major like the qkv buffer they are cut from: [2 (k, v), layers, R, Lmax, H * d_kv] bf16.
+        alt_cache: also a second cache of the same shape — a step whose ``parents`` live on the device re-orders the cache by copying
+        it into the other buffer (ops.kv_gather_rows: parents repeat, so not in place) and swaps the two."""
         c = self.cfg
         assert max_len <= 128, "incremental decode: the shifted relative-position LUT covers 128 positions"
         inner = c.t5_heads * c.d_kv
@@ -1954,13 +1956,18 @@ class MrBlipEngine:
             # launch but position t of the sequence: a base pointer moved back by t gives lut[(key - t) + 128] (no clamp can trigger
             # below 128 positions); 128 floats of front padding keep the moved pointer inside the allocation
             self.lut_dec_pad = torch.cat([torch.zeros(128, dtype=f32, device=self.dev), self.lut_dec.reshape(-1)])
-        return {"kv": kv, "t": 0, "R": R, "Lmax": Lmax}
+        state = {"kv": kv, "t": 0, "R": R, "Lmax": Lmax}
+        if alt_cache:
+            state["kv_alt"] = self.buf("g_self_kv_alt", kv.shape, bf16)
+        return state
 
     @torch.no_grad()
     @_with_attention_split
     def t5_decode_step(self, state: dict, tokens: torch.Tensor, parents: Optional[torch.Tensor], cross_cache, cross_batch: int, kmask):
         """One decoder position for R sequences: tokens [R] (the newest token of each), parents [R] (row of the previous call each
-        sequence extends; None = unchanged order) -> fp32 logits [R, vocab] of the next token.  modeling_t5.py:747-826 with
+        sequence extends; None = unchanged order) -> fp32 logits [R, vocab] of the next token.  Host tensors, or DEVICE tensors (int32:
+        tokens index the embedding table as they are, parents always gather the cache into the state's second buffer — nothing is
+        uploaded or compared, so the host never waits; needs t5_decode_begin(alt_cache=True)).  modeling_t5.py:747-826 with
         use_cache=True: the new position's K / V are appended to the cache, the query attends to positions 0..t (nothing to mask: the
         causal mask of the last row is empty), cross-attention reads the per-clip K / V of t5_cross_kv."""
         c = self.cfg
@@ -1968,7 +1975,12 @@ class MrBlipEngine:
         inner = H * dk
         R, t, kv, Lmax = state["R"], state["t"], state["kv"], state["Lmax"]
         assert not self.training and tokens.numel() == R and t < Lmax
-        if parents is not None and t > 0 and not torch.equal(parents, torch.arange(R)):
+        if parents is not None and parents.is_cuda:
+            assert parents.dtype == torch.int32 and parents.numel() == R and "kv_alt" in state, "device parents: int32 [R] and t5_decode_begin(alt_cache=True)"
+            if t > 0:
+                ops.kv_gather_rows(kv, state["kv_alt"], parents, t)
+                kv, state["kv"], state["kv_alt"] = state["kv_alt"], state["kv_alt"], kv
+        elif parents is not None and t > 0 and not torch.equal(parents, torch.arange(R)):
             kv[:, :, :, :t] = kv[:, :, :, :t].index_select(2, self.h2d(parents, torch.int64))
         rows = torch.arange(R, dtype=torch.int32, device=self.dev)
         x = self.buf("s_x", (R, d), f32, zero=False)

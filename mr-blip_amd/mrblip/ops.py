@@ -120,6 +120,10 @@ class QformerLayer(C.Structure):
 
 
 _qf_layer_fwd = _sig("mrblip_qformer_layer_fwd", C.POINTER(QformerLayer), vp)
+_beam_topk = _sig("mrblip_beam_topk", vp, ll, vp, vp, ll, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, ll, vp)
+_beam_advance = _sig("mrblip_beam_advance", vp, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp)
+_beam_finalize = _sig("mrblip_beam_finalize", vp, ll, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp)
+_kv_gather_rows = _sig("mrblip_kv_gather_rows", vp, vp, vp, i32, i32, i32, i32, i32, vp)
 
 EXPORTS = [
     "mrblip_last_error", "mrblip_abi_version", "mrblip_gemm_bf16", "mrblip_layernorm_fwd", "mrblip_rmsnorm_fwd",
@@ -132,6 +136,7 @@ EXPORTS = [
     "mrblip_gemm_ksplit", "mrblip_rmsnorm_bwd_parts", "mrblip_rmsnorm_bwd_parts_g", "mrblip_set_reduce_workspace", "mrblip_reduce_workspace_bytes", "mrblip_gemm_clear_one_shots", "mrblip_gated_gelu_bwd_parts", "mrblip_sum_parts",
     "mrblip_qformer_layer_fwd", "mrblip_layernorm_bwd_cast",
     "mrblip_gemm_f16", "mrblip_layernorm_fwd_f16", "mrblip_attention_fwd_rowv_f16", "mrblip_patchify_f16", "mrblip_patchify_u8_f16",
+    "mrblip_beam_topk", "mrblip_beam_advance", "mrblip_beam_finalize", "mrblip_kv_gather_rows",
 ]
 
 
@@ -810,3 +815,49 @@ def lora_dx_add(dx, G, acat, drop: Optional[Dropout] = None):
     M, K = dx.shape
     sp, site, p = _d(drop)
     _chk(_lora_dx(_p(dx), _ld(dx), 1 if dx.dtype == torch.float32 else 0, _p(G), _ld(G), _p(acat), acat.shape[0], M, K, sp, site, p, _stream()))
+
+
+# ---- device-resident beam search (csrc/search.hip; driven by mrblip.search.DeviceBeamSearch)
+BEAM_CHUNK = 2048   # vocabulary entries per selection workgroup
+
+
+def beam_topk_workspace_bytes(R: int, K: int, V: int) -> int:
+    return 4 * R * ((V + BEAM_CHUNK - 1) // BEAM_CHUNK) * (2 + 4 * K)
+
+
+def beam_topk(logits, beam_scores, seqs, cur_len: int, K: int, cand_score, cand_index, ws, *, min_length: int = 1, eos_id: int = 1,
+              repetition_penalty: float = 1.0):
+    """cand_score / cand_index [R / K, 2K] <- per clip the 2K best of log_softmax(logits) (+ repetition penalty over seqs[:, :cur_len], EOS
+    masked while cur_len < min_length) + beam_scores, best first, equal scores by lower flat index beam * V + token.  logits fp32 [R, V];
+    seqs int32 [R, >= cur_len]; ws: uint8 scratch of beam_topk_workspace_bytes(R, K, V)."""
+    R, V = logits.shape
+    _req(logits, torch.float32, "beam_topk.logits")
+    _req(seqs, torch.int32, "beam_topk.seqs")
+    _chk(_beam_topk(_p(logits), _ld(logits), _p(beam_scores), _p(seqs), _ld(seqs), R, int(K), V, int(cur_len), int(min_length), int(eos_id),
+                    float(repetition_penalty), _p(cand_score), _p(cand_index), _p(ws), ws.numel() * ws.element_size(), _stream()))
+
+
+def beam_advance(cand_score, cand_index, seq_in, seq_out, beam_scores, parents, tokens, pool_score, pool_len, pool_seq, pool_n, done, done_count,
+                 B: int, K: int, V: int, cur_len: int, len_pow: float, *, eos_id: int = 1, pad_id: int = 0):
+    """one search step of every clip on the device state (search.py:134-160); len_pow = cur_len ** length_penalty"""
+    assert _ld(seq_in) == _ld(seq_out) == pool_seq.stride(1)
+    _chk(_beam_advance(_p(cand_score), _p(cand_index), _p(seq_in), _p(seq_out), _ld(seq_in), _p(beam_scores), _p(parents), _p(tokens), _p(pool_score),
+                       _p(pool_len), _p(pool_seq), _p(pool_n), _p(done), _p(done_count), int(B), int(K), int(V), int(cur_len), int(eos_id), int(pad_id),
+                       float(len_pow), _stream()))
+
+
+def beam_finalize(seq, beam_scores, pool_score, pool_len, pool_seq, pool_n, done, B: int, K: int, cur_len: int, len_pow: float, num_return: int, out):
+    """out int32 [B, num_return, ld + 2] <- {length, score bits, tokens} of every clip's best hypotheses (search.py:164-170)"""
+    assert _ld(seq) == pool_seq.stride(1) and out.stride(1) == _ld(seq) + 2 and out.is_contiguous()
+    _chk(_beam_finalize(_p(seq), _ld(seq), _p(beam_scores), _p(pool_score), _p(pool_len), _p(pool_seq), _p(pool_n), _p(done), int(B), int(K), int(cur_len),
+                        float(len_pow), int(num_return), _p(out), _stream()))
+
+
+def kv_gather_rows(src, dst, parents, t: int):
+    """dst[..., r, :t, :] = src[..., parents[r], :t, :] for contiguous bf16 caches [..., R, Lmax, inner]; parents int32 on the device"""
+    _req(src, torch.bfloat16, "kv_gather_rows.src")
+    _req(parents, torch.int32, "kv_gather_rows.parents")
+    assert src.is_contiguous() and dst.is_contiguous() and src.shape == dst.shape and dst.dtype == src.dtype and src.dim() >= 3
+    R, Lmax, inner = src.shape[-3:]
+    assert parents.numel() == R
+    _chk(_kv_gather_rows(_p(src), _p(dst), _p(parents), src.numel() // (R * Lmax * inner), R, Lmax, inner, int(t), _stream()))

@@ -90,7 +90,7 @@ def sample_search(step_fn: Callable[[torch.Tensor], torch.Tensor], batch: int, n
 
 def beam_search(step_fn: Callable[[torch.Tensor], torch.Tensor], batch: int, num_beams: int, max_new_tokens: int, min_length: int = 1,
                 length_penalty: float = 1.0, eos_id: int = 1, pad_id: int = 0, start_id: int = 0, trace: Optional[list] = None,
-                repetition_penalty: float = 1.0, num_return: int = 1) -> List[torch.Tensor]:
+                repetition_penalty: float = 1.0, num_return: int = 1, detail: Optional[list] = None) -> List[torch.Tensor]:
     """step_fn(seqs [batch * K, L] int64) -> log-probabilities [batch * K, V] (float32, CPU) of the next token.
     A step function with a truthy ``takes_parents`` attribute is called as step_fn(seqs, parents): parents [batch * K] int64 names, for
     every row of ``seqs``, the row of the PREVIOUS call it extends (None on the first call) — what an incremental decoder needs to
@@ -98,6 +98,9 @@ def beam_search(step_fn: Callable[[torch.Tensor], torch.Tensor], batch: int, num
     trace (diagnostics, optional list): receives one entry per step — for every batch item the 2K best candidate scores, best first
     (entry[b][K-1] - entry[b][K] is the margin by which the K-th beam survived the pruning) — and a last entry with every item's final
     pool scores, best first; tests use it to tell a genuine tie from a wrong result.
+    detail (diagnostics, optional list): one entry per step — for every batch item (None once it is done) a dict with ``idx`` (the flat
+    indices beam * V + token of the 2K best, in ``trace``'s order), ``next`` (score of the (2K+1)-th candidate, -inf if there is none) and
+    ``absmax`` (largest finite |candidate score| over the item's live beams, i.e. those not at the -1e9 placeholder).
     repetition_penalty: HF's processor on the log-probabilities of the tokens already in each beam.  num_return (<= num_beams): the
     ``num_return_sequences`` best hypotheses of every item, best first (HF's BeamSearchScorer.finalize).
     Returns num_return 1-D tensors per batch item (item-major): start token, generated tokens, EOS if the hypothesis ended with one."""
@@ -131,6 +134,11 @@ def beam_search(step_fn: Callable[[torch.Tensor], torch.Tensor], batch: int, num
         top, idx = cand.topk(min(2 * K, K * V), dim=-1)
         if trace is not None:
             trace.append([None if done[b] else top[b].tolist() for b in range(B)])
+        if detail is not None:
+            nxt = cand.topk(2 * K + 1, dim=-1)[0][:, -1].tolist() if K * V > 2 * K else [-float("inf")] * B
+            live = (beam_scores > -1e8).view(B, K, 1).expand(B, K, V).reshape(B, K * V) & torch.isfinite(cand)
+            absmax = cand.abs().masked_fill(~live, 0.0).amax(-1).tolist()
+            detail.append([None if done[b] else dict(idx=idx[b].tolist(), next=nxt[b], absmax=absmax[b]) for b in range(B)])
         new_seqs = torch.full((B * K, cur_len + 1), pad_id, dtype=torch.long)
         new_scores = torch.zeros(B, K)
         parents = torch.arange(B * K)
@@ -171,3 +179,153 @@ def beam_search(step_fn: Callable[[torch.Tensor], torch.Tensor], batch: int, num
     if trace is not None:
         trace.append([sorted((sc for sc, _ in pools[b]), reverse=True) for b in range(B)])
     return out
+
+
+class DeviceBeamSearch:
+    """``beam_search`` with its whole state in device memory (csrc/search.hip): the candidate selection over [B * K, V] logits, the beam /
+    hypothesis-pool bookkeeping and the `done` rule run as HIP kernels, so a decoding loop never waits for the host:
+
+        search = DeviceBeamSearch(B, K, max_new, ...)
+        for _ in range(max_new):
+            if search.finished():                       # polls an event, never waits
+                break
+            logits = decoder(search.tokens, search.parents)      # device int32 [B * K]: newest token / row of the previous step
+            search.step(logits)                                   # RAW fp32 logits [B * K, V] (the log-softmax is part of the kernel)
+            search.done_count_async()
+        hyps = search.finalize()                                  # the one blocking transfer
+
+    The constructor mirrors ``beam_search``; ``finalize`` returns what it returns.  Ties: equal candidate scores rank by lower flat index
+    beam * V + token, equal pool scores by lower pool slot.  State comes from ``buf`` (a named-workspace allocator such as
+    ``Engine.buf``: ``buf(name, shape, dtype)``) or from plain tensors on ``device``.
+
+    State layout (int32 unless noted): seq [2, B * K, L] ping-pong halves of the running sequences (L = max_new + 1, start token first);
+    scores fp32 [B, K]; parents / tokens [B * K]; pool_score fp32 / pool_len [B, K], pool_seq [B, K, L], pool_n [B]; done [B];
+    done_count [1]; candidates of the current step: cand_score fp32 / cand_index [B, 2K]; selection scratch (bytes)."""
+
+    def __init__(self, batch: int, num_beams: int, max_new_tokens: int, min_length: int = 1, length_penalty: float = 1.0, eos_id: int = 1,
+                 pad_id: int = 0, start_id: int = 0, repetition_penalty: float = 1.0, num_return: int = 1, device=None, buf=None,
+                 poll_lag: int = 2):
+        from mrblip import ops
+        self._ops = ops
+        B, K = int(batch), max(1, int(num_beams))
+        assert 1 <= K <= 16, "DeviceBeamSearch: 1..16 beams"
+        assert 1 <= int(num_return) <= K, "num_return_sequences has to be smaller or equal to num_beams"
+        assert int(max_new_tokens) >= 1
+        self.B, self.K, self.R, self.max_new, self.L = B, K, B * K, int(max_new_tokens), int(max_new_tokens) + 1
+        self.min_length, self.length_penalty, self.repetition_penalty = int(min_length), float(length_penalty), float(repetition_penalty)
+        self.eos_id, self.pad_id, self.start_id, self.num_return = int(eos_id), int(pad_id), int(start_id), int(num_return)
+        self.poll_lag = int(poll_lag)
+        self.device = torch.device(device if device is not None else "cuda")
+        self._buf = buf
+        R, L = self.R, self.L
+        i32, f32 = torch.int32, torch.float32
+        # ONE int32 and ONE fp32 block, so that a reset is two fills
+        n_int = [("seq", 2 * R * L), ("parents", R), ("tokens", R), ("pool_len", R), ("pool_seq", R * L), ("pool_n", B), ("done", B),
+                 ("done_count", 1), ("cand_index", 2 * R), ("out", B * self.num_return * (L + 2))]
+        n_f32 = [("scores", R), ("pool_score", R), ("cand_score", 2 * R)]
+        self._ints = self._alloc("bs_ints", sum(n for _, n in n_int), i32)
+        self._f32s = self._alloc("bs_f32s", sum(n for _, n in n_f32), f32)
+        for block, parts in ((self._ints, n_int), (self._f32s, n_f32)):
+            off = 0
+            for name, n in parts:
+                setattr(self, "_" + name, block[off:off + n])
+                off += n
+        self._seq = self._seq.view(2, R, L)
+        self._pool_seq = self._pool_seq.view(B, K, L)
+        self._out = self._out.view(B, self.num_return, L + 2)
+        self._identity = torch.arange(R, dtype=i32, device=self.device)
+        self._ws = None
+        # early stop without blocking: the done counter of every step lands in a pinned slot of its own, behind an event
+        self._slots = torch.full((self.max_new,), -1, dtype=i32).pin_memory()
+        self._events = [torch.cuda.Event() for _ in range(self.max_new)]
+        self.reset()
+
+    def _alloc(self, name, n, dtype):
+        if self._buf is not None:
+            return self._buf(name, (n,), dtype)
+        return torch.zeros(n, dtype=dtype, device=self.device)
+
+    def reset(self):
+        """back to the state before the first step (start token, beam 0 at score 0 and the others at -1e9, empty pools).  Only enqueues."""
+        self._ints.zero_()
+        self._f32s.zero_()
+        if self.start_id != 0:
+            self._seq[0, :, 0].fill_(self.start_id)
+            self._tokens.fill_(self.start_id)
+        if self.K > 1:
+            self._scores.view(self.B, self.K)[:, 1:].fill_(-1e9)
+        self._parents.copy_(self._identity)
+        self._slots.fill_(-1)
+        self.cur_len, self.steps, self._recorded, self._finalized, self.host_seconds = 1, 0, 0, False, 0.0
+
+    # the decoder's inputs for the next step
+    @property
+    def tokens(self) -> torch.Tensor:
+        return self._tokens
+
+    @property
+    def parents(self) -> torch.Tensor:
+        return self._parents
+
+    @property
+    def sequences(self) -> torch.Tensor:
+        """int32 [B * K, cur_len] view of the running sequences (start token first)"""
+        return self._seq[self.steps & 1][:, :self.cur_len]
+
+    def step(self, logits_dev: torch.Tensor):
+        """raw fp32 next-token logits [B * K, V] of the current rows -> new beams; launches only"""
+        import time
+        t0 = time.perf_counter()
+        ops = self._ops
+        assert not self._finalized and self.steps < self.max_new, "DeviceBeamSearch.step: past max_new_tokens (or after finalize)"
+        R, V = logits_dev.shape
+        assert R == self.R
+        if self._ws is None or self._ws.numel() < ops.beam_topk_workspace_bytes(R, self.K, V):
+            self._ws = self._alloc("bs_ws", ops.beam_topk_workspace_bytes(R, self.K, V), torch.uint8)
+        src, dst = self._seq[self.steps & 1], self._seq[(self.steps + 1) & 1]
+        ops.beam_topk(logits_dev, self._scores, src, self.cur_len, self.K, self._cand_score, self._cand_index, self._ws, min_length=self.min_length,
+                      eos_id=self.eos_id, repetition_penalty=self.repetition_penalty)
+        ops.beam_advance(self._cand_score, self._cand_index, src, dst, self._scores, self._parents, self._tokens, self._pool_score, self._pool_len,
+                         self._pool_seq, self._pool_n, self._done, self._done_count, self.B, self.K, V, self.cur_len,
+                         float(self.cur_len) ** self.length_penalty, eos_id=self.eos_id, pad_id=self.pad_id)
+        self.steps += 1
+        self.cur_len += 1
+        self.host_seconds += time.perf_counter() - t0
+
+    def done_count_async(self):
+        """enqueue the copy of the done counter after the last step into that step's pinned slot, and record the step's event"""
+        i = self.steps - 1
+        assert i >= 0 and self._recorded == i, "done_count_async: once after every step"
+        self._slots[i:i + 1].copy_(self._done_count, non_blocking=True)
+        self._events[i].record()
+        self._recorded = i + 1
+
+    def finished(self) -> bool:
+        """True when the step ``poll_lag`` before the next one is known to have left every clip done (event QUERIED, never waited for)"""
+        i = self.steps - self.poll_lag
+        if i < 0 or i >= self._recorded or not self._events[i].query():
+            return False
+        return int(self._slots[i]) == self.B
+
+    def steps_after_done(self) -> int:
+        """after finalize: steps that were enqueued although every clip was already done (the price of not waiting)"""
+        assert self._finalized
+        for i in range(self._recorded):
+            if int(self._slots[i]) == self.B:
+                return self.steps - (i + 1)
+        return 0
+
+    def finalize(self) -> List[torch.Tensor]:
+        import time
+        t0 = time.perf_counter()
+        assert not self._finalized and self.steps >= 1
+        self._ops.beam_finalize(self._seq[self.steps & 1], self._scores, self._pool_score, self._pool_len, self._pool_seq, self._pool_n, self._done,
+                                self.B, self.K, self.cur_len, float(self.cur_len - 1) ** self.length_penalty, self.num_return, self._out)
+        self._finalized = True
+        self.host_seconds += time.perf_counter() - t0
+        out = self._out.cpu()                                    # the one blocking transfer: everything enqueued has run after it
+        t0 = time.perf_counter()
+        self.final_scores = out[:, :, 1].contiguous().view(torch.float32)
+        hyps = [out[b, r, 2:2 + int(out[b, r, 0])].to(torch.long) for b in range(self.B) for r in range(self.num_return)]
+        self.host_seconds += time.perf_counter() - t0
+        return hyps
