@@ -140,6 +140,15 @@ int mrblip_patchify_u8(const uint8_t* video, const float* mean3, const float* st
 int mrblip_patchify_f16(const float* video, void* out_f16, int F, int IMG, int P, int Kpad, mrblip_stream_t stream);
 int mrblip_patchify_u8_f16(const uint8_t* video, const float* mean3, const float* std3, void* out_f16, int F, int IMG, int P, int Kpad,
                            mrblip_stream_t stream);
+/* Train-split augmentation on the device (blip_processors.py:287-312, transforms_video.py RandomResizedCropVideo): uint8 frames
+ * src [F,3,H,W] -> dst [F,3,OUT,OUT], frame f cropped to box f / frames_per_clip and resized with torch's bicubic
+ * (upsample_bicubic2d, align_corners=False, A = -0.75, taps clamped to the CROP), fp32 accumulation, clamp to [0,255], truncating cast.
+ * boxes_host: HOST array of n_clips x (i, j, h, w) = top, left, height, width in source pixels; it travels by value in the kernel
+ * arguments (n_clips <= 64) and is validated here (h, w >= 1, box inside the frame), so there is no upload and no device-side error
+ * path.  F == n_clips * frames_per_clip, H, W <= 4096, 1 <= OUT <= 1024, src 4-B aligned.  A full-frame box with H == W == OUT
+ * returns src bit for bit.  Same bits on every run. */
+int mrblip_crop_resize_u8(const uint8_t* src, int F, int H, int W, const int* boxes_host, int n_clips, int frames_per_clip, uint8_t* dst,
+                          int OUT, mrblip_stream_t stream);
 /* x = [cls ; patches] + pos  (eva_vit.py:328-331) */
 int mrblip_vit_assemble(const float* patch, const float* cls, const float* pos, float* x, int F, int NP, int D, mrblip_stream_t stream);
 /* dst[dst_idx[i],:] (=|+=) src[src_idx[i],:]; src_idx<0 -> zeros.  Embedding gathers and the frame/timestamp

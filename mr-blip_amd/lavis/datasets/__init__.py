@@ -61,14 +61,20 @@ class MomentRetrievalDataset(_MRBase):
     ToTensor + Normalize is fused into the patch-embed load on the GPU (a quarter of the H2D bytes).
 
     ``crop_scale`` = (min_scale, max_scale) switches on the train processor's augmentation (Blip2VideoTrainProcessor,
-    blip_processors.py:287-312): one RandomResizedCrop per clip, bicubic, shared by all frames; None (eval splits) = frames as decoded."""
+    blip_processors.py:287-312): one RandomResizedCrop per clip, bicubic, shared by all frames; None (eval splits) = frames as decoded.
 
-    def __init__(self, ann_path, vis_root, n_frms=60, image_size=224, frame_loader=None, sampling="uniform", video_ext=".mp4", crop_scale=None):
+    ``device_crop=True`` (with ``crop_scale``): the box (i, j, h, w) is drawn exactly as above — same call, same rng, so a run picks the
+    same boxes in either mode — but the frames are returned UNCROPPED with ``"crop_box"`` (int32 [4]); the model crops and resizes them
+    on the GPU (Blip2MR._frames_to_device -> ops.crop_resize_u8), which takes the bicubic arithmetic off the loader's cores."""
+
+    def __init__(self, ann_path, vis_root, n_frms=60, image_size=224, frame_loader=None, sampling="uniform", video_ext=".mp4", crop_scale=None,
+                 device_crop=False):
         self.ann = json.load(open(ann_path))
         self.vis_root, self.T, self.img = vis_root, n_frms, image_size
         self.frame_loader = frame_loader or default_frame_loader
         self.sampling, self.ext = sampling, video_ext
         self.crop_scale = tuple(float(x) for x in crop_scale) if crop_scale else None
+        self.device_crop = bool(device_crop)
 
     def __len__(self):
         return len(self.ann)
@@ -89,11 +95,18 @@ class MomentRetrievalDataset(_MRBase):
             u8, idx, fps = self.frame_loader(self._path(a["video"]), self.T, self.img, sampling=self.sampling, clip_proposal=clip)
         except TypeError:  # a user-supplied loader with the short signature
             u8, idx, fps = self.frame_loader(self._path(a["video"]), self.T, self.img)
-        if self.crop_scale is not None:
+        box = None
+        if self.crop_scale is not None and self.device_crop:
+            from lavis.datasets.data_utils import random_resized_crop_params
+            box = random_resized_crop_params(u8.shape[-2], u8.shape[-1], scale=self.crop_scale)
+        elif self.crop_scale is not None:
             from lavis.datasets.data_utils import random_resized_crop_u8
             u8 = random_resized_crop_u8(u8, self.img, scale=self.crop_scale)
         ts = torch.tensor([round(float(k / fps), 2) for k in idx])
-        return self._sample(u8, ts, a["duration"], a["query"], a["relevant_windows"], a["qid"])
+        s = self._sample(u8, ts, a["duration"], a["query"], a["relevant_windows"], a["qid"])
+        if box is not None:
+            s["crop_box"] = torch.tensor(box, dtype=torch.int32)
+        return s
 
 
 class _Builder:
@@ -123,7 +136,9 @@ class MomentRetrievalBuilder(_Builder):
     """lavis/datasets/builders/moment_retrieval_builder.py:16-23 + base_dataset_builder.py: one MomentRetrievalDataset per annotation
     split; the TRAIN split gets the train processor (random frame per interval + one RandomResizedCrop per clip, scale
     [min_scale, max_scale] = [0.5, 1.0] unless the vis_processor config says otherwise), every other split the eval processor
-    (middle frame per interval, no crop).  Splits whose annotation file does not exist are skipped with a warning."""
+    (middle frame per interval, no crop).  ``vis_processor.train.device_crop: True`` (default False) hands the train split's frames on
+    uncropped with their crop box, for the model to crop on the GPU.  Splits whose annotation file does not exist are skipped with a
+    warning."""
 
     def build_datasets(self):
         info = self.config.build_info
@@ -136,7 +151,8 @@ class MomentRetrievalBuilder(_Builder):
             vp = vps.get("train" if is_train else "eval", None) or vps.get("train", None) or vps.get("eval", None) or {}
             crop = (vp.get("min_scale", 0.5), vp.get("max_scale", 1.0)) if is_train and vp.get("name", "blip2_video_train") == "blip2_video_train" else None
             out[split] = MomentRetrievalDataset(ann.storage, info.videos.storage, n_frms=vp.get("n_frms", 60), image_size=vp.get("image_size", 224),
-                                                sampling="random" if is_train else "uniform", crop_scale=crop)
+                                                sampling="random" if is_train else "uniform", crop_scale=crop,
+                                                device_crop=bool(is_train and vp.get("device_crop", False)))
         if not out:
             import logging
             logging.warning("%s builder: none of the annotation files %s exists — no dataset was built", type(self).__name__,

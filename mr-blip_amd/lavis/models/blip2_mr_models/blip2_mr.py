@@ -324,10 +324,20 @@ class BLIP2_MR(BaseModel):
         return P.build_layout(self.t5_tokenizer, samples, self.annoying_numbers_replacement_dict, n, T, self.max_txt_len,
                               no_task_prompt="no_task_prompt" in self.task, time_format=self.input_time_format, interleave=bool(self.interleave_data))
 
-    def _frames_to_device(self, v):
+    def _frames_to_device(self, v, crop_box=None):
         """fp32 frames already normalised by the processor (the reference's contract), or raw uint8 frames [B,T,3,H,W]: those stay uint8 —
-        a quarter of the H2D bytes — and ToTensor + Normalize(CLIP mean/std) is fused into the patch-embed load."""
-        return v.to(self._device) if v.dtype == torch.uint8 else v.to(self._device, torch.float32)
+        a quarter of the H2D bytes — and ToTensor + Normalize(CLIP mean/std) is fused into the patch-embed load.
+
+        ``crop_box`` (int [B,4] of i, j, h, w per clip; the dataset's ``device_crop`` mode): the uint8 frames arrive UNCROPPED, of any
+        H x W, and the train processor's RandomResizedCrop + bicubic resize runs here on the device (ops.crop_resize_u8) -> uint8
+        [B,T,3,img,img]; everything downstream sees the same tensor the loader-side crop would have produced."""
+        if crop_box is None:
+            return v.to(self._device) if v.dtype == torch.uint8 else v.to(self._device, torch.float32)
+        if v.dtype != torch.uint8:
+            raise ValueError(f"crop_box needs raw uint8 frames: the device crop runs before ToTensor + Normalize, but the frames are {v.dtype} "
+                             "(already normalised)")
+        from mrblip import ops
+        return ops.crop_resize_u8(v.to(self._device).contiguous(), torch.as_tensor(crop_box).cpu(), self.engine.cfg.img)
 
     _staged_next = None  # (host tensor of the next batch's frames, its device copy): see forward()
     _reserved = False    # engine workspaces sized for the longest step (first forward)
@@ -344,14 +354,16 @@ class BLIP2_MR(BaseModel):
 
     def forward(self, samples):
         """samples: the reference's dict (blip2_mr.py:433-445).  Optional extra key ``next_video``: the NEXT batch's frames (the train
-        loop's one-batch look-ahead, tasks/moment_retrieval.py); its frozen-ViT forward is overlapped with this step's T5 decoder."""
+        loop's one-batch look-ahead, tasks/moment_retrieval.py); its frozen-ViT forward is overlapped with this step's T5 decoder.
+        Optional ``crop_box`` / ``next_crop_box`` (int [B,4]): uncropped uint8 frames to crop + resize on the device (_frames_to_device);
+        generate() and the QA path ignore them — eval splits are never cropped."""
         if self.is_qa:
             return self.forward_QA(samples)
         src = samples["video"]
         if self._staged_next is not None and self._staged_next[0] is src:
             video = self._staged_next[1]  # the device copy whose ViT features were prefetched during the previous step
         else:
-            video = self._frames_to_device(src)
+            video = self._frames_to_device(src, samples.get("crop_box"))
         self._staged_next = None
         layout = self._layout(samples)
         if not self._reserved:
@@ -369,7 +381,7 @@ class BLIP2_MR(BaseModel):
         nxt = samples.get("next_video") if need_grad else None
         nxt_dev = None
         if nxt is not None:
-            nxt_dev = self._frames_to_device(nxt)
+            nxt_dev = self._frames_to_device(nxt, samples.get("next_crop_box"))  # (the staged copy is the CROPPED tensor: one crop per clip)
             self._staged_next = (nxt, nxt_dev)
         loss = _TrainStep.apply(self.trainable_decay, self.trainable_no_decay, self, video, layout, need_grad, nxt_dev)
         return {"loss": loss}

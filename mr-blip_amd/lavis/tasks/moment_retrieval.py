@@ -71,6 +71,8 @@ class MomentRetrievalTask(BaseTask):
             samples.update({"epoch": epoch, "num_iters_per_epoch": iters_per_epoch, "iters": i})
             if nxt is not None:  # one-batch look-ahead: the model overlaps the next clip's frozen-ViT forward with this step's decoder
                 samples["next_video"] = nxt["video"]
+                if nxt.get("crop_box") is not None:  # device_crop datasets: the look-ahead crops the next clip once, on the device
+                    samples["next_crop_box"] = nxt["crop_box"]
             lr_scheduler.step(cur_epoch=epoch, cur_step=i)
             if arm_exchange is not None and (i + 1) % accum_grad_iters == 0:
                 arm_exchange()  # this micro-step closes the window: its backward starts the (overlapped) gradient all-reduce

@@ -124,6 +124,7 @@ _beam_topk = _sig("mrblip_beam_topk", vp, ll, vp, vp, ll, i32, i32, i32, i32, i3
 _beam_advance = _sig("mrblip_beam_advance", vp, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp)
 _beam_finalize = _sig("mrblip_beam_finalize", vp, ll, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp)
 _kv_gather_rows = _sig("mrblip_kv_gather_rows", vp, vp, vp, i32, i32, i32, i32, i32, vp)
+_crop_resize_u8 = _sig("mrblip_crop_resize_u8", vp, i32, i32, i32, C.POINTER(C.c_int), i32, i32, vp, i32, vp)
 
 EXPORTS = [
     "mrblip_last_error", "mrblip_abi_version", "mrblip_gemm_bf16", "mrblip_layernorm_fwd", "mrblip_rmsnorm_fwd",
@@ -137,6 +138,7 @@ EXPORTS = [
     "mrblip_qformer_layer_fwd", "mrblip_layernorm_bwd_cast",
     "mrblip_gemm_f16", "mrblip_layernorm_fwd_f16", "mrblip_attention_fwd_rowv_f16", "mrblip_patchify_f16", "mrblip_patchify_u8_f16",
     "mrblip_beam_topk", "mrblip_beam_advance", "mrblip_beam_finalize", "mrblip_kv_gather_rows",
+    "mrblip_crop_resize_u8",
 ]
 
 
@@ -707,6 +709,44 @@ def patchify(video: torch.Tensor, out: torch.Tensor, patch: int, mean=CLIP_MEAN,
         _chk((_patchify_u8_f16 if f16 else _patchify_u8)(_p(video), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), _p(out), F_, IMG, patch, out.shape[1], _stream()))
     else:
         _chk((_patchify_f16 if f16 else _patchify)(_p(video), _p(out), F_, IMG, patch, out.shape[1], _stream()))
+
+
+def crop_resize_u8(src_u8: torch.Tensor, boxes, out_size: int, out: Optional[torch.Tensor] = None, frames_per_clip: Optional[int] = None) -> torch.Tensor:
+    """The train processor's RandomResizedCrop + bicubic resize on the device (csrc/augment.hip), the arithmetic of
+    lavis.datasets.data_utils.random_resized_crop_u8.  src_u8: uint8 [n_clips, T, 3, H, W], or [F, 3, H, W] with ``frames_per_clip``
+    (default: one clip).  boxes: CPU int tensor / list [n_clips, 4] of (i, j, h, w) = top, left, height, width — host values, passed in
+    the kernel arguments (no upload, no synchronisation).  -> uint8 [..., 3, out_size, out_size] (``out`` if given)."""
+    if src_u8.dim() == 5:
+        n_clips, fpc = src_u8.shape[0], src_u8.shape[1]
+        if frames_per_clip is not None and frames_per_clip != fpc:
+            raise MrblipError(f"crop_resize_u8: frames_per_clip = {frames_per_clip} contradicts the [n_clips, T, ...] input {tuple(src_u8.shape)}")
+    elif src_u8.dim() == 4:
+        fpc = int(frames_per_clip) if frames_per_clip is not None else src_u8.shape[0]
+        n_clips = src_u8.shape[0] // fpc if fpc > 0 and src_u8.shape[0] % fpc == 0 else -1
+    else:
+        raise MrblipError(f"crop_resize_u8: expected [n_clips, T, 3, H, W] or [F, 3, H, W] frames, got {tuple(src_u8.shape)}")
+    if src_u8.shape[-3] != 3:
+        raise MrblipError(f"crop_resize_u8: expected 3 channels, got {tuple(src_u8.shape)}")
+    b = torch.as_tensor(boxes)
+    if b.is_cuda or b.is_floating_point() or b.dim() != 2 or b.shape[1] != 4:
+        raise MrblipError(f"crop_resize_u8: boxes must be a CPU integer [n_clips, 4] tensor or list of (i, j, h, w), got {b.dtype} {tuple(b.shape)} on {b.device}")
+    if n_clips != b.shape[0]:
+        raise MrblipError(f"crop_resize_u8: {src_u8.shape[0] if src_u8.dim() == 4 else n_clips * fpc} frames are not n_clips * frames_per_clip = {b.shape[0]} * {fpc}")
+    flat = [int(v) for v in b.reshape(-1).tolist()]
+    _req(src_u8, torch.uint8, "crop_resize_u8 src")
+    if not src_u8.is_contiguous():
+        raise MrblipError("crop_resize_u8: src must be contiguous")
+    H, W = src_u8.shape[-2:]
+    F_ = n_clips * fpc
+    shape = tuple(src_u8.shape[:-2]) + (out_size, out_size)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src_u8.device)
+    else:
+        _req(out, torch.uint8, "crop_resize_u8 out")
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise MrblipError(f"crop_resize_u8: out must be a contiguous uint8 {shape} tensor, got {tuple(out.shape)}")
+    _chk(_crop_resize_u8(_p(src_u8), F_, H, W, (C.c_int * len(flat))(*flat), n_clips, fpc, _p(out), int(out_size), _stream()))
+    return out
 
 
 def vit_assemble(patch, cls, pos, x):

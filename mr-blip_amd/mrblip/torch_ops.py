@@ -15,6 +15,8 @@ the standard PyTorch extension point:
   mrblip::cross_entropy(logits, labels) -> loss  fp32 [R,V], int32 [R] (-100 = ignore) -> mean over valid rows, fp32 [1]
   mrblip::adamw_(p, g, m, v, hyper, ...)         in-place fused AdamW over flat fp32 buffers
   mrblip::gemm_(a, w, out, bias?, residual?, act, tile_cfg)   the raw fused GEMM, writing ``out`` in place
+  mrblip::crop_resize_u8(src, boxes, out_size, frames_per_clip) -> dst   uint8 [.., 3, H, W] -> [.., 3, out, out]: one crop box per clip
+                                                 (CPU int [n_clips, 4] of i, j, h, w) + bicubic resize; input augmentation, no autograd
 
 Every operator has a fake (meta) implementation, so FakeTensor tracing / torch.compile graph capture see shapes and dtypes without
 running a kernel.  CUDA (= HIP) tensors only: there is no CPU fallback, by design.
@@ -279,5 +281,18 @@ def _(p, g, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
     return None
 
 
+# ------------------------------------------------------------------------------------------------ input augmentation
+@custom_op("mrblip::crop_resize_u8", mutates_args=(), device_types="cuda")
+def crop_resize_u8(src: torch.Tensor, boxes: torch.Tensor, out_size: int, frames_per_clip: int = 0) -> torch.Tensor:
+    """src: uint8 [n_clips, T, 3, H, W], or [F, 3, H, W] with frames_per_clip > 0; boxes: CPU int [n_clips, 4] (host values: they travel
+    in the kernel arguments).  No gradient: the frames are data."""
+    return ops.crop_resize_u8(_c(src), boxes, out_size, frames_per_clip=frames_per_clip or None)
+
+
+@crop_resize_u8.register_fake
+def _(src, boxes, out_size, frames_per_clip=0):
+    return src.new_empty(tuple(src.shape[:-2]) + (out_size, out_size))
+
+
 OPS = ("gemm_", "linear", "linear_backward", "layer_norm", "layer_norm_backward", "rms_norm", "rms_norm_backward", "attention_forward",
-       "attention_backward", "cross_entropy_forward", "adamw_")
+       "attention_backward", "cross_entropy_forward", "adamw_", "crop_resize_u8")
