@@ -1573,8 +1573,7 @@ static bool use_lds64(const AttnArgs& a, int flags) {
 }
 
 static int attn_ks2_mode() {  // MRB_ATTN_KS2: 0 = never, 1 = always, unset = when there are too few query tiles to give every SIMD four waves
-  const char* e = getenv("MRB_ATTN_KS2");   // (read per launch: tests pin the choice while they compare runs of different batch sizes)
-  return e ? atoi(e) : -1;
+  return mrb_env_int("MRB_ATTN_KS2", -1);   // (read per launch, NOT cached: tests pin the choice while they compare runs of different batch sizes)
 }
 template <int FL>
 static void fwd_lds64(const AttnArgs& a, dim3 grid, hipStream_t stream) {
@@ -1643,8 +1642,7 @@ static int attn_xs_split(const AttnArgs& a, bool split) {
 // keys, one block per head: decoder phases 8.79 + 13.96 ms with 4 waves, 8.85 + 14.21 ms with 8, step 70.44 vs 70.52 ms — the block is
 // bound by what ONE CU streams, not by the length of a wave's tile chain; off by default)
 static bool attn_split8(const AttnArgs& a) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("MRB_ATTN_SPLIT8"); on = (e && e[0] == '1') ? 1 : 0; }
+  static const bool on = mrb_env_on("MRB_ATTN_SPLIT8");
   return on && a.Sk >= 1024;
 }
 

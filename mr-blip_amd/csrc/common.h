@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -42,6 +43,35 @@ char* mrblip_reduce_workspace();   // the calling thread's registered workspace 
       return MRBLIP_EINVAL;               \
     }                                     \
   } while (0)
+
+// ---- host-side launch layer: what every launch site needs besides its kernel (definitions: errors.hip)
+int mrb_num_cus();   // CUs of the current device, queried once per process (256 if the query fails: the launch that follows reports the device's state)
+
+// Library-side MRB_* switches: five parsing rules.  A site reads its switch ONCE per process into a `static const` (thread-safe), except
+// where a comment says otherwise.
+bool mrb_env_on(const char* name);                // default off: a value that starts with '1' turns it on
+bool mrb_env_not_off(const char* name);           // default on: a value that starts with '0' turns it off
+bool mrb_env_present(const char* name);           // on when the variable exists, whatever it holds
+int mrb_env_int(const char* name, int dflt);      // atoi of the value, dflt when unset
+bool mrb_env_equals(const char* name, int value); // set, and atoi of the value == value
+
+// Launch Kernel with `lds` bytes of dynamic LDS; before the instantiation's first launch raise the kernel's dynamic-LDS limit to lds_max
+// (>= every lds this kernel is launched with).  The once-flag belongs to the instantiation, i.e. to the kernel.  Threads that race for the
+// first launch (forward and autograd thread) each raise the limit themselves — the call is idempotent — so none launches before it is set;
+// a failed call is tried again by the next launch.  `what` names the kernel in both error texts.
+template <auto Kernel, class... Args>
+static int mrb_launch_lds(const char* what, int lds_max, dim3 grid, dim3 block, int lds, hipStream_t stream, const Args&... args) {
+  static std::atomic<bool> raised{false};
+  if (!raised.load(std::memory_order_acquire)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
+      mrblip_set_error("%s: cannot raise dynamic LDS to %d", what, lds_max);
+      return MRBLIP_ELAUNCH;
+    }
+    raised.store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+  return mrblip_check_launch(what);
+}
 
 // ---- bf16 <-> f32 (round-to-nearest-even, like torch .bfloat16())
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }

@@ -684,6 +684,18 @@ static void dp_drop(DropoutArg& d, const uint32_t* seed_ptr, uint32_t site, floa
   d.inv_keep = 1.0f / (1.0f - p);
 }
 
+// the two kernels' launches.  Dynamic-LDS limit: the widest form of the instantiation (mode 2's two weight tiles, a 2048-wide row block)
+template <int MODE, int XM, int UB>
+static int launch_dp2(const DecProjArgs& a, int tpb, int grid, int lds, hipStream_t stream) {
+  constexpr int LDS_MAX = 2 * 8 * 2 * 1024 + 8 * 2 * 1024 + 1024 + 16 * (2048 * 2 + 16);
+  return mrb_launch_lds<dec_proj2_kernel<MODE, XM, UB>>("dec_proj", LDS_MAX, dim3(grid), dim3(512), lds, stream, a, tpb);
+}
+template <int NT, int MODE, int UB, int RT>
+static int launch_dp(const DecProjArgs& a, int grid, int lds, hipStream_t stream) {
+  constexpr int LDS_MAX = 8 * (2 * NT + 2) * 64 * 16 + 1024 + 16 * (2048 * 2 + 16);
+  return mrb_launch_lds<dec_proj_kernel<NT, MODE, UB, RT>>("dec_proj", LDS_MAX, dim3(grid), dim3(512), lds, stream, a);
+}
+
 // mode: 0 = bf16 out, 1 = fp32 out (+ residual), 2 = gated (W / Bt hold 2 N rows: wi_0 then wi_1; out2 [R, 2 N], optional, receives the pre-activations).
 // x32 != NULL: RMSNorm(x32) * gamma is the input (K <= 2048) and is saved to xin; else xin is the bf16 input.  ext_p > 0: the LoRA-backward
 // form (the rank-Rk product masked per element before it is added).  R <= 16 (<= 80 without the fused RMSNorm / gating), N % 16 == 0, K % 32 == 0, Rk <= 32 and a multiple of 8.
@@ -715,75 +727,47 @@ extern "C" int mrblip_dec_proj(const float* x32, long long ldx32, const float* g
   dp_drop(a.out_drop, seed_ptr, out_site, out_p);
   dp_drop(a.ext_drop, seed_ptr, ext_site, ext_p);
   // round 4: R <= 16 rows take the streaming kernel (MRB_DEC_PROJ_V2=0: the one-tile-per-block kernel of round 3)
-  if (g_dec_v2 < 0) { const char* e = getenv("MRB_DEC_PROJ_V2"); g_dec_v2 = (e && e[0] == '0') ? 0 : 1; }
+  if (g_dec_v2 < 0) g_dec_v2 = mrb_env_not_off("MRB_DEC_PROJ_V2") ? 1 : 0;
   if (g_dec_v2 && R <= 16) {
-    static int ncu = 0, env_grid = -1;
-    if (ncu == 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    if (env_grid < 0) { const char* e = getenv("MRB_DEC_GRID"); env_grid = e ? atoi(e) : 0; }
-    const int G = env_grid > 0 ? env_grid : (g_dec_grid > 0 ? g_dec_grid : ncu);
+    static const int env_grid = mrb_env_int("MRB_DEC_GRID", 0);
+    const int G = env_grid > 0 ? env_grid : (g_dec_grid > 0 ? g_dec_grid : mrb_num_cus());
     const int tiles = (N + 15) / 16;
     const int tpb = (tiles + G - 1) / G;
     const int grid2 = (tiles + tpb - 1) / tpb;
     const bool xl = K <= 2048;
     const int ntw2 = mode == 2 ? 2 : 1;
     const int LDS2 = 2 * 8 * ntw2 * 1024 + 8 * 2 * 1024 + 1024 + (xl ? 16 * (K * 2 + 16) : 0);
-    static bool attr2[9] = {};
-#define MRB_DP2_LAUNCH(ID, MODE_, XM_, UB_)                                                                                       \
-  {                                                                                                                                \
-    auto k = dec_proj2_kernel<MODE_, XM_, UB_>;                                                                                    \
-    if (!attr2[ID]) {                                                                                                              \
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 2 * 1024 + 8 * 2 * 1024 + 1024 + 16 * (2048 * 2 + 16)) != hipSuccess) { \
-        mrblip_set_error("dec_proj: cannot raise dynamic LDS");                                                                    \
-        return MRBLIP_ELAUNCH;                                                                                                     \
-      }                                                                                                                            \
-      attr2[ID] = true;                                                                                                            \
-    }                                                                                                                              \
-    hipLaunchKernelGGL(k, dim3(grid2), dim3(512), LDS2, stream, a, tpb);                                                           \
-  }
     const int xm = !xl ? 0 : (x32 ? 2 : 1);
-    if (mode == 2) { if (xm == 2) MRB_DP2_LAUNCH(0, 2, 2, 4) else if (xm == 1) MRB_DP2_LAUNCH(1, 2, 1, 4) else MRB_DP2_LAUNCH(2, 2, 0, 4) }
-    else if (mode == 0) { if (xm == 2) MRB_DP2_LAUNCH(3, 0, 2, 8) else if (xm == 1) MRB_DP2_LAUNCH(4, 0, 1, 8) else MRB_DP2_LAUNCH(5, 0, 0, DP2_UB_LONGK) }
-    else { if (xm == 2) MRB_DP2_LAUNCH(6, 1, 2, 8) else if (xm == 1) MRB_DP2_LAUNCH(7, 1, 1, 8) else MRB_DP2_LAUNCH(8, 1, 0, DP2_UB_LONGK) }
-#undef MRB_DP2_LAUNCH
-    return mrblip_check_launch("dec_proj");
+    if (mode == 2) {
+      if (xm == 2) return launch_dp2<2, 2, 4>(a, tpb, grid2, LDS2, stream);
+      if (xm == 1) return launch_dp2<2, 1, 4>(a, tpb, grid2, LDS2, stream);
+      return launch_dp2<2, 0, 4>(a, tpb, grid2, LDS2, stream);
+    }
+    if (mode == 0) {
+      if (xm == 2) return launch_dp2<0, 2, 8>(a, tpb, grid2, LDS2, stream);
+      if (xm == 1) return launch_dp2<0, 1, 8>(a, tpb, grid2, LDS2, stream);
+      return launch_dp2<0, 0, DP2_UB_LONGK>(a, tpb, grid2, LDS2, stream);
+    }
+    if (xm == 2) return launch_dp2<1, 2, 8>(a, tpb, grid2, LDS2, stream);
+    if (xm == 1) return launch_dp2<1, 1, 8>(a, tpb, grid2, LDS2, stream);
+    return launch_dp2<1, 0, DP2_UB_LONGK>(a, tpb, grid2, LDS2, stream);
   }
   // 32 output columns per block; 16 (twice the blocks, half the weight bytes each) for the long-K projections of a 2048-wide output, whose
   // 64 blocks are otherwise a serial stream of 20-40 k-steps per wave (MRB_DEC_PROJ_NT1=0 keeps 32)
-  static int nt1 = -1;
-  if (nt1 < 0) { const char* e = getenv("MRB_DEC_PROJ_NT1"); nt1 = (e && e[0] == '0') ? 0 : 1; }
+  static const bool nt1 = mrb_env_not_off("MRB_DEC_PROJ_NT1");
   const int rt = R <= 16 ? 1 : R <= 48 ? 3 : 5;
   const bool narrow = nt1 && mode != 2 && K >= 4096 && N <= 4096 && rt == 1;
   const int nt = narrow ? 1 : 2;
   const int grid = (N + 16 * nt - 1) / (16 * nt);
   const int ntw = mode == 2 ? 2 * nt : nt;
   const int LDS = 8 * (ntw + 2) * 64 * 16 + 1024 + (x32 ? 16 * (K * 2 + 16) : 0);
-  static bool attr[16] = {};
-#define MRB_DP_LAUNCH(ID, NT_, MODE_, UB_, RT_)                                                                                    \
-  {                                                                                                                                \
-    auto k = dec_proj_kernel<NT_, MODE_, UB_, RT_>;                                                                                \
-    if (!attr[ID]) {                                                                                                               \
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * (2 * NT_ + 2) * 64 * 16 + 1024 + 16 * (2048 * 2 + 16)) != hipSuccess) { \
-        mrblip_set_error("dec_proj: cannot raise dynamic LDS");                                                                    \
-        return MRBLIP_ELAUNCH;                                                                                                     \
-      }                                                                                                                            \
-      attr[ID] = true;                                                                                                             \
-    }                                                                                                                              \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), LDS, stream, a);                                                                  \
+  if (mode == 2) return launch_dp<2, 2, 2, 1>(a, grid, LDS, stream);
+  if (mode == 0) {
+    if (rt == 1) return narrow ? launch_dp<1, 0, 4, 1>(a, grid, LDS, stream) : launch_dp<2, 0, 4, 1>(a, grid, LDS, stream);
+    if (rt == 3) return launch_dp<2, 0, 2, 3>(a, grid, LDS, stream);
+    return launch_dp<2, 0, 1, 5>(a, grid, LDS, stream);
   }
-  if (mode == 2) MRB_DP_LAUNCH(0, 2, 2, 2, 1)
-  else if (mode == 0) {
-    if (rt == 1) { if (narrow) MRB_DP_LAUNCH(1, 1, 0, 4, 1) else MRB_DP_LAUNCH(2, 2, 0, 4, 1) }
-    else if (rt == 3) MRB_DP_LAUNCH(3, 2, 0, 2, 3)
-    else MRB_DP_LAUNCH(4, 2, 0, 1, 5)
-  } else {
-    if (rt == 1) { if (narrow) MRB_DP_LAUNCH(5, 1, 1, 4, 1) else MRB_DP_LAUNCH(6, 2, 1, 4, 1) }
-    else if (rt == 3) MRB_DP_LAUNCH(7, 2, 1, 2, 3)
-    else MRB_DP_LAUNCH(8, 2, 1, 1, 5)
-  }
-#undef MRB_DP_LAUNCH
-  return mrblip_check_launch("dec_proj");
+  if (rt == 1) return narrow ? launch_dp<1, 1, 4, 1>(a, grid, LDS, stream) : launch_dp<2, 1, 4, 1>(a, grid, LDS, stream);
+  if (rt == 3) return launch_dp<2, 1, 2, 3>(a, grid, LDS, stream);
+  return launch_dp<2, 1, 1, 5>(a, grid, LDS, stream);
 }

@@ -2,6 +2,7 @@
 #include "common.h"
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 static thread_local char g_err[512] = "";
 
@@ -20,6 +21,21 @@ int mrblip_check_launch(const char* what) {
   }
   return MRBLIP_OK;
 }
+
+int mrb_num_cus() {
+  static const int n = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+  }();
+  return n;
+}
+
+bool mrb_env_on(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+bool mrb_env_not_off(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
+bool mrb_env_present(const char* name) { return getenv(name) != nullptr; }
+int mrb_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+bool mrb_env_equals(const char* name, int value) { const char* e = getenv(name); return e && atoi(e) == value; }
 
 static thread_local char* g_reduce_ws = nullptr;
 char* mrblip_reduce_workspace() { return g_reduce_ws; }

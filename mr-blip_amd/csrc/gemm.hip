@@ -1377,10 +1377,10 @@ __global__ __launch_bounds__(256, 1) void gemm_w16_kernel(const GemmArgs p) {
 #else
 #define W4D_STORE_GUARD
 #endif
-#ifndef W4D_S_SWAP
-#define W4D_S_SWAP 24
-#define W4D_S_STORE 25
-#define W4D_S_SHIFT 26
+#ifndef W4D_STEP_SWAP
+#define W4D_STEP_SWAP 24
+#define W4D_STEP_STORE 25
+#define W4D_STEP_SHIFT 26
 #define W4D_SHIFT_PER 4
 #endif
 template <int ACT>
@@ -1445,14 +1445,14 @@ __global__ __launch_bounds__(256, 1) void gemm_w4d_kernel(const GemmArgs p) {
           ARR[i_] = pack2bf(y_[0], y_[1]);                                                                             \
         }                                                                                                                \
       }                                                                                                                  \
-    } else if ((S) == W4D_S_SWAP) {                                                                                        \
+    } else if ((S) == W4D_STEP_SWAP) {                                                                                        \
       _Pragma("unroll") for (int gp_ = 0; gp_ < 2; ++gp_)                                                                \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) {                                                               \
           auto r_ = __builtin_amdgcn_permlane32_swap(ARR[(2 * gp_) * 2 + h_], ARR[(2 * gp_ + 1) * 2 + h_], false, false); \
           ARR[(2 * gp_) * 2 + h_] = r_[0];                                                                                \
           ARR[(2 * gp_ + 1) * 2 + h_] = r_[1];                                                                            \
         }                                                                                                                \
-    } else if ((S) == W4D_S_STORE) {                                                                                        \
+    } else if ((S) == W4D_STEP_STORE) {                                                                                        \
       const int blk_ = blk_cur;                           /* (mt, nt) = (blk / 4, blk % 4) */                            \
       const int row_ = st_row + (blk_ >> 2) * 32 + l31;                                                                  \
       const int col_ = st_col + (blk_ & 3) * 32 + 8 * hi;                                                                \
@@ -1461,9 +1461,9 @@ __global__ __launch_bounds__(256, 1) void gemm_w4d_kernel(const GemmArgs p) {
         if (col_ < p.N) *reinterpret_cast<uint4*>(o_) = make_uint4(ARR[0], ARR[1], ARR[2], ARR[3]);                          \
         if (col_ + 16 < p.N) *reinterpret_cast<uint4*>(o_ + 16) = make_uint4(ARR[4], ARR[5], ARR[6], ARR[7]);                \
       }                                                                                                                  \
-    } else if ((S) >= W4D_S_SHIFT && (NSH) > 0) {                                                                        \
+    } else if ((S) >= W4D_STEP_SHIFT && (NSH) > 0) {                                                                        \
       _Pragma("unroll") for (int m_ = 0; m_ < W4D_SHIFT_PER; ++m_) {                                                     \
-        const int b_ = ((S) - W4D_S_SHIFT) * W4D_SHIFT_PER + m_;                                                         \
+        const int b_ = ((S) - W4D_STEP_SHIFT) * W4D_SHIFT_PER + m_;                                                         \
         if (b_ < 8 * (NPARK - 1)) stash[b_] = stash[b_ + 8];                                                             \
       }                                                                                                                  \
     }                                                                                                                    \
@@ -1763,19 +1763,16 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const GemmArgs p) 
 }
 
 static bool pf_tail_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("MRB_GEMM_PF_TAIL"); on = (e && e[0] == '1') ? 1 : 0; }
-  return on == 1;
+  static const bool on = mrb_env_on("MRB_GEMM_PF_TAIL");
+  return on;
 }
 static bool thin_ticket_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("MRB_GEMM_THIN_TICKET"); on = (e && e[0] == '1') ? 1 : 0; }
-  return on == 1;
+  static const bool on = mrb_env_on("MRB_GEMM_THIN_TICKET");
+  return on;
 }
 static bool roles_last_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("MRB_GEMM_ROLES_LAST"); on = (e && e[0] == '0') ? 0 : 1; }
-  return on == 1;
+  static const bool on = mrb_env_not_off("MRB_GEMM_ROLES_LAST");
+  return on;
 }
 
 template <int BM, int BN, int WGM, int WGN, bool OUT_F32, bool GATED, int BK = 64, int NS = 2>
@@ -1784,29 +1781,11 @@ static int launch_tile(GemmArgs& a, hipStream_t st) {
   const int ncols = GATED ? a.N / 2 : a.N;
   a.tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (ncols + BNO - 1) / BNO;
-  {
-    static int env_gm = -1;
-    if (env_gm < 0) { const char* e = getenv("MRB_GROUP_M"); env_gm = e ? atoi(e) : 0; }
-    a.group_m = env_gm > 0 ? env_gm : 8;
-  }
+  static const int env_gm = mrb_env_int("MRB_GROUP_M", 0);
+  a.group_m = env_gm > 0 ? env_gm : 8;
   constexpr int TN_ = BN / WGN / 32, SLAB = 32 * (TN_ * 32 * 4 + 16) * WGM * WGN;   // epilogue staging (see the kernel)
   constexpr int LDS = NS * (BM + BN) * BK * 2 > SLAB ? NS * (BM + BN) * BK * 2 : SLAB;
-  auto kern = gemm_tile_kernel<BM, BN, WGM, WGN, OUT_F32, GATED, BK, NS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      mrblip_set_error("gemm: cannot raise dynamic LDS to %d", LDS);
-      return MRBLIP_ELAUNCH;
-    }
-    attr_set = true;
-  }
-  static int num_cu = 0;
-  if (num_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { mrblip_set_error("gemm: cannot query device"); return MRBLIP_ELAUNCH; }
-    num_cu = prop.multiProcessorCount;
-  }
+  const int num_cu = mrb_num_cus();
   // 256x256 (one block per CU): persistent, one block per CU walks the tiles.  128x128: one block per tile (the hardware's dynamic
   // dispatch of 2 blocks/CU measured slightly faster than a static persistent walk).
   const int ntiles = a.tiles_m * a.tiles_n;
@@ -1844,8 +1823,7 @@ static int launch_tile(GemmArgs& a, hipStream_t st) {
     }
   }
   static_assert(LDS >= THIN_RED_BYTES(2), "the thin role's partial sums live in the tile's LDS");
-  hipLaunchKernelGGL(kern, dim3(grid + a.pf_blocks + a.th_blocks), dim3(WGM * WGN * 64), LDS, st, a);
-  return mrblip_check_launch("gemm_tile");
+  return mrb_launch_lds<gemm_tile_kernel<BM, BN, WGM, WGN, OUT_F32, GATED, BK, NS>>("gemm_tile", LDS, dim3(grid + a.pf_blocks + a.th_blocks), dim3(WGM * WGN * 64), LDS, st, a);
 }
 
 static void mk_drop_arg(DropoutArg& d, const uint32_t* seed_ptr, uint32_t site, float p) {
@@ -1867,7 +1845,6 @@ extern "C" int mrblip_gemm_set_cu_reserve(int n_cus) {
   return prev;
 }
 
-// shared by the C entry points: validation, tile selection, launch.  ext_first / ext_* / a_* : see GemmArgs.
 // one-shot extras of the calling thread's NEXT mrblip_gemm_bf16 / mrblip_gemm_lora_dx launch (round 4): see GemmArgs.tout / ext_group_n
 struct GemmExtra { void* tout[3]; int t_inner, t_rows, t_spad; long long t_bs, t_hs, t_stride; int t_count, ext_group_n; bool set; };
 static thread_local GemmExtra g_gemm_extra = {};
@@ -1925,6 +1902,252 @@ extern "C" int mrblip_gemm_clear_one_shots(void) {
   return MRBLIP_OK;
 }
 
+// ---- the launch side of gemm_dispatch / mrblip_gemm_ksplit --------------------------------------------------------------------------
+// what a call asks for besides the operands in GemmArgs: read by select_cfg and by the launchers
+struct GemmCall {
+  bool out_f32, gated, f16;
+  int requested;     // tile_cfg & 0xff as the caller passed it (0 = auto)
+  int reserve_arg;   // per-call CU reserve (see mrblip_gemm_set_cu_reserve)
+  int k_splits;      // skinny kernel: K split with atomic accumulation into a pre-initialised fp32 output
+  hipStream_t stream;
+};
+
+// Grid of a persistent launch over `units` tiles: the CUs the reserve leaves (at least 8), or the tiles rounded up to a multiple of 8.
+// g_cu_reserve: CUs this persistent kernel leaves alone (mrblip_gemm_set_cu_reserve).  Its blocks hold a whole CU each for the
+// whole launch (all 512 registers of every SIMD), so kernels of another stream can only start on CUs it does not occupy: the
+// frozen-ViT look-ahead of the train step gives the clip that is being trained a quarter of the chip this way.
+// (a multiple of 8: the same number of blocks on every XCD.  Measured and dropped in round 3: shrinking the grid to the fewest CUs
+// that keep the round count — ceil(tiles / rounds): ViT fc1 1464 tiles = 8 rounds on 184 CUs as on 192 — so that the other stream
+// gets the difference: +0.3 ms per step; the CUs of a partly filled last round are not idle, they go to the other stream EARLIER.)
+static int mrb_persistent_grid(int units, int reserve_arg) {
+  const int reserve = reserve_arg ? reserve_arg / 8 * 8 : g_cu_reserve;
+  const int cus = mrb_num_cus() - reserve > 8 ? mrb_num_cus() - reserve : 8;
+  return units < cus ? (units + 7) / 8 * 8 : cus;
+}
+
+// A generic tile config: the fp32-out, bf16-out or gated instantiation of one tile shape.  Shapes without a gated form (no_gated = their
+// message) reject `gated` and instantiate no gated kernel.
+template <bool HAS_GATED, int BM, int BN, int WGM, int WGN, int BK = 64, int NS = 2>
+static int launch_tile_cfg(GemmArgs& a, const GemmCall& q, const char* no_gated = nullptr) {
+  if constexpr (HAS_GATED) {
+    if (q.gated) return launch_tile<BM, BN, WGM, WGN, false, true, BK, NS>(a, q.stream);
+  } else {
+    MRB_REQUIRE(!q.gated, "%s", no_gated);
+  }
+  return q.out_f32 ? launch_tile<BM, BN, WGM, WGN, true, false, BK, NS>(a, q.stream) : launch_tile<BM, BN, WGM, WGN, false, false, BK, NS>(a, q.stream);
+}
+
+static int launch_skinny(GemmArgs& a, const GemmCall& q) {
+  MRB_REQUIRE(!q.gated, "gemm: skinny kernel has no gated epilogue");
+  const int M = a.M, N = a.N;
+  // rows of the tall operand per block: 32, fewer when the grid would leave most CUs idle (LoRA down / g products at M = 2012)
+  int rpb = 32;
+  static const bool rpb32 = mrb_env_present("MRB_SKINNY_RPB32");
+  while (!rpb32 && rpb > 8 && (long long)((N + 31) / 32) * ((M + rpb - 1) / rpb) < 192 && M > rpb) rpb >>= 1;
+  a.m_rows_per_block = rpb;
+  dim3 grid((N + 31) / 32, (M + rpb - 1) / rpb);
+  if (q.k_splits > 1) {
+    MRB_REQUIRE(q.out_f32 && !a.residual && !a.out2 && a.act == 0, "gemm: the K-split form adds into a pre-initialised fp32 output (no residual / out2 / act)");
+    a.k_splits = q.k_splits;
+    grid.z = q.k_splits;
+  }
+  // (a 16-wave K-split changes nothing here: with one lane per operand row these launches are bound by the number of row-gather
+  // load instructions one CU's address unit can retire, not by a wave's sequential load rounds)
+  // (measured and dropped for the tall-and-thin LoRA products of the encoder, M = 2012, N <= 32: one block per 32 rows with 16 waves
+  // splitting K - all lanes of every load and dropout hash valid, 4 waves per CU - 10.9 vs 12.4 us at K = 2048 but 38 vs 25 us at
+  // K = 10240, +0.4 ms per step: profiles/r02_skinny_tall16.txt)
+  if (q.out_f32) hipLaunchKernelGGL((gemm_skinny_kernel<true, 4>), grid, dim3(256), 0, q.stream, a);
+  else hipLaunchKernelGGL((gemm_skinny_kernel<false, 4>), grid, dim3(256), 0, q.stream, a);
+  return mrblip_check_launch("gemm_skinny");
+}
+
+// The instantiations of gemm_w4_kernel that exist, found by their template arguments: W4 spells them once for the case label and for the
+// kernel, so the two cannot get out of step.
+constexpr int w4_key(bool f32, int act, bool res, int tn, bool f16 = false, bool w3 = false, bool split = false, bool gated = false) {
+  return (f32 ? 1 : 0) | (res ? 2 : 0) | (f16 ? 4 : 0) | (w3 ? 8 : 0) | (split ? 16 : 0) | (gated ? 32 : 0) | (act << 6) | (tn << 8);
+}
+static int launch_w4(const char* what, const GemmArgs& a, int key, int grid, int lds, hipStream_t stream) {
+#define W4(...) \
+  case w4_key(__VA_ARGS__): return mrb_launch_lds<gemm_w4_kernel<__VA_ARGS__>>(what, lds, dim3(grid), dim3(256), lds, stream, a);
+  switch (key) {
+    // <OUT_F32, ACT, RES, TN>: 256x256 tiles (TN = 4, cfg 13) and 256x192 tiles (TN = 3, cfg 14)
+    W4(false, 0, false, 4) W4(false, 0, true, 4) W4(false, 1, false, 4) W4(false, 1, true, 4)
+    W4(true, 0, false, 4) W4(true, 0, true, 4) W4(true, 1, false, 4) W4(true, 1, true, 4)
+    W4(false, 0, false, 3) W4(false, 0, true, 3) W4(false, 1, false, 3) W4(false, 1, true, 3)
+    W4(true, 0, false, 3) W4(true, 0, true, 3) W4(true, 1, false, 3) W4(true, 1, true, 3)
+    // fp16 operands (ViT): qkv (bf16-sized out + bias), fc1 (+ GELU), proj / fc2 (fp32 residual stream), patch embedding (fp32 out + bias)
+    W4(false, 0, false, 4, true) W4(false, 1, false, 4, true) W4(true, 0, false, 4, true) W4(true, 0, true, 4, true)
+    // three W stages (cfg 17): the frozen ViT's four bf16 forms
+    W4(false, 0, false, 4, false, true) W4(false, 1, false, 4, false, true) W4(true, 0, false, 4, false, true) W4(true, 0, true, 4, false, true)
+    // gated-GELU (T5 wi_0 / wi_1): bf16 y + bf16 pre-activations, dropout
+    W4(false, 0, false, 4, false, false, false, true)
+    // K-split (mrblip_gemm_ksplit): 256x256, 256x192 and 256x128 tiles; 256x256 with three W stages
+    W4(false, 0, false, 4, false, false, true) W4(true, 0, false, 4, false, false, true)
+    W4(false, 0, false, 3, false, false, true) W4(true, 0, false, 3, false, false, true)
+    W4(false, 0, false, 2, false, false, true) W4(true, 0, false, 2, false, false, true)
+    W4(false, 0, false, 4, false, true, true) W4(true, 0, false, 4, false, true, true)
+  }
+#undef W4
+  mrblip_set_error("gemm: no such 4-wave kernel variant (%d)%s", key, (key & w4_key(false, 0, false, 0, true)) ? " - the fp16 form exists for bias / bias+GELU (16-bit out) and fp32 out with or without residual" : "");
+  return MRBLIP_EINVAL;
+}
+
+// cfg 13 / 14 / 17: four waves of 128 x 128 (cfg 13, 256x256 tile) / 128 x 96 (cfg 14, 256x192), hand-pipelined K loop.
+// cfg 17 (round 4): cfg 13 with a third stage buffer for the W operand (gemm_w4_kernel W3).  Measured (profiles/r04_w3_bench.txt):
+// bit-identical; with the chip to itself equal within noise (8192^3 1426 vs 1426 TFLOP/s, fc1 252.5 vs 250.5 us, fc2 298 vs 303 us);
+// on the 192 CUs the look-ahead runs on: 8192^3 1217 vs 1140 TFLOP/s, fc2 280 vs 285 us, fc1 in the step 340 vs 348 us; step 70.48 vs
+// 70.45 ms.  So the late W pieces were NOT what the K loop waits for; the form is kept as the library's choice for an automatic cfg 13
+// because it is never slower where it runs (select_cfg; MRB_W4_W3=0: two stages; an explicit tile_cfg 13 always means two stages)
+static int launch_w4_cfg(GemmArgs& a, const GemmCall& q, int cfg) {
+  const int M = a.M, N = a.N;
+  const bool gated = q.gated, out_f32 = q.out_f32, f16 = q.f16;
+  bool w3 = cfg == 17;
+  if (cfg == 17) cfg = 13;
+  MRB_REQUIRE(gated || (!a.Aext && !a.out2 && !a.drop.seed_ptr), "gemm: cfg 13 / 14 take plain epilogues only (or the gated-GELU form of cfg 13)");
+  MRB_REQUIRE(!gated || (cfg == 13 && !a.Aext && !f16 && (N % 16) == 0 && (!a.out2 || (long long)M * a.ldo2 * 2 < (1ll << 31))),
+              "gemm: the gated form of the 4-wave kernel is cfg 13 on bf16 operands without a K extension ([x | u] x [W | B]^T instead)");
+  MRB_REQUIRE(a.act == 0 || a.act == 1, "gemm: cfg 13 / 14 know act 0 / 1");
+  MRB_REQUIRE((long long)M * a.ldo * (out_f32 ? 4 : 2) < (1ll << 31) && (!a.residual || (long long)M * a.ldr * 4 < (1ll << 31)),
+              "gemm: cfg 13 / 14 address output and residual through 2 GiB buffer resources");
+  const int bn13 = cfg == 13 ? 256 : 192;
+  a.tiles_m = (M + 255) / 256;
+  a.tiles_n = gated ? (N / 2 + 127) / 128 : (N + bn13 - 1) / bn13;      // (gated: 128 output columns per tile)
+  if (gated) w3 = false;
+  const int stage13 = (256 + bn13) * 128, slab13 = 4 * 32 * (bn13 / 2 * 4 + 16);
+  MRB_REQUIRE(!w3 || (cfg == 13 && !f16), "gemm: the three-W-stage form (cfg 17) exists for the bf16 256x256 tile");
+  const int LDS = w3 ? 2 * stage13 + 256 * 128 : (2 * stage13 > stage13 + slab13 ? 2 * stage13 : stage13 + slab13);
+  const int grid = mrb_persistent_grid(a.tiles_m * a.tiles_n, q.reserve_arg);
+  const int key = gated ? w4_key(false, 0, false, 4, false, false, false, true) : w4_key(out_f32, a.act, a.residual != nullptr, cfg == 13 ? 4 : 3, f16, w3);
+  return launch_w4("gemm_w4", a, key, grid, LDS, q.stream);
+}
+
+// cfg 15: cfg 13's tile with the deferred epilogue (bf16 out, bias, optional GELU, no residual): ViT qkv / fc1
+static int launch_w4d_cfg(GemmArgs& a, const GemmCall& q) {
+  MRB_REQUIRE(!q.gated && !a.Aext && !a.out2 && !a.drop.seed_ptr && !q.out_f32 && !a.residual && (a.act == 0 || a.act == 1), "gemm: cfg 15 = bf16 out, bias, optional GELU only");
+  a.tiles_m = (a.M + 255) / 256;
+  a.tiles_n = (a.N + 255) / 256;
+  const int LDS = 2 * (256 + 256) * 128;
+  const dim3 grid(mrb_persistent_grid(a.tiles_m * a.tiles_n, q.reserve_arg));
+  if (a.act == 1) return mrb_launch_lds<gemm_w4d_kernel<1>>("gemm_w4d", LDS, grid, dim3(256), LDS, q.stream, a);
+  return mrb_launch_lds<gemm_w4d_kernel<0>>("gemm_w4d", LDS, grid, dim3(256), LDS, q.stream, a);
+}
+
+// cfg 16: cfg 13's tile on 16x16x32 MFMAs
+template <bool F32, int ACT>
+static int launch_w16(const GemmArgs& a, dim3 grid, hipStream_t stream) {
+  constexpr int LDS = 2 * (256 + 256) * 128;
+  if (a.residual) return mrb_launch_lds<gemm_w16_kernel<F32, ACT, true>>("gemm_w16", LDS, grid, dim3(256), LDS, stream, a);
+  return mrb_launch_lds<gemm_w16_kernel<F32, ACT, false>>("gemm_w16", LDS, grid, dim3(256), LDS, stream, a);
+}
+static int launch_w16_cfg(GemmArgs& a, const GemmCall& q) {
+  MRB_REQUIRE(!q.gated && !a.Aext && !a.out2 && !a.drop.seed_ptr && (a.act == 0 || a.act == 1), "gemm: cfg 16 takes plain epilogues only");
+  a.tiles_m = (a.M + 255) / 256;
+  a.tiles_n = (a.N + 255) / 256;
+  const dim3 grid(mrb_persistent_grid(a.tiles_m * a.tiles_n, q.reserve_arg));
+  if (q.out_f32) return a.act == 1 ? launch_w16<true, 1>(a, grid, q.stream) : launch_w16<true, 0>(a, grid, q.stream);
+  return a.act == 1 ? launch_w16<false, 1>(a, grid, q.stream) : launch_w16<false, 0>(a, grid, q.stream);
+}
+
+// Part 2 of gemm_dispatch: the tile config a call runs with.  No launch in here.
+// tile_cfg: 0 auto, 1 = 256x256 (8 waves, persistent), 2 = 128x128, 3 = skinny, 4 = 64x128, 5 = 64x64, 8 = 256x256 with 16 waves,
+// 13 = 256x256 with 4 waves (plain epilogues); measured and not auto-selected:
+// 6 = 256x256 with 4 waves of 128x128 (1 wave/SIMD: 0.7x), 7 = 256x128 BK=32 3-stage (= 128x128), [128x128 BK=32 at 3-4 blocks/CU: 0.8x,
+// 256x128 / 128x256 BK=64 with one 4-wave block per CU: 0.6x; 256x128 / 128x256 BK=32 with 8 waves of 64x64, two blocks per CU: 0.7x]
+static int select_cfg(const GemmArgs& a, const GemmCall& q, int& cfg) {
+  const int M = a.M, N = a.N, K = a.K, act = a.act;
+  const bool gated = q.gated, f16 = q.f16;
+  const bool has_drop = a.drop.seed_ptr != nullptr;   // p_drop > 0 (gemm_dispatch has checked that it comes with a seed pointer)
+  cfg = q.requested;
+  if (f16) {   // IEEE fp16 operands: the frozen ViT's GEMMs, which all take the 4-wave 256x256 kernel with a plain epilogue
+    MRB_REQUIRE(cfg == 0 || cfg == 13, "gemm_f16: only the 4-wave 256x256 kernel (tile_cfg 0 / 13) has an fp16 form");
+    cfg = 13;
+  }
+  if (cfg == 0) {
+    if (M <= 64 && !gated) cfg = 3;
+    else {
+      // measured on MI355X (tools/gemm_bench.py, tools/gemm_kfit.py): the 256x256 kernel (1 block/CU) only wins for long-K, many-tile
+      // problems; 128x128 (2 blocks/CU hide each other's staging latency and epilogue) wins at the ViT shapes; outputs with fewer
+      // 128x128 tiles than resident block slots (T5 [2012,2048], Q-Former [1920,768]) are tile-starved -> 64x128 / 64x64 tiles.
+      const int ncols = gated ? N / 2 : N;
+      const long long t256 = (long long)((M + 255) / 256) * ((ncols + (gated ? 127 : 255)) / (gated ? 128 : 256));
+      const long long t128 = (long long)((M + 127) / 128) * ((ncols + (gated ? 63 : 127)) / (gated ? 64 : 128));
+      const long long t64x128 = (long long)((M + 63) / 64) * ((ncols + (gated ? 63 : 127)) / (gated ? 64 : 128));
+      // 256x256 with 16 waves of 64x64 (4 waves per SIMD hide each other's LDS-DMA issue; half the L2->LDS bytes per flop of 128x128)
+      // is the fastest main loop, but it runs one block per CU: it pays only when its rounds are full (ViT fc1: 1464 tiles = 5.7
+      // rounds of 256 CUs) or when one partial round covers most CUs (T5 qkv: 192 tiles)
+      const int ncu = mrb_num_cus();
+      const long long rounds = (t256 + ncu - 1) / ncu;
+      const double eff256 = (double)t256 / (double)(rounds * ncu);
+      static const bool no8 = mrb_env_present("MRB_NO_CFG8");
+      if (!no8 && !gated && K >= 1024 && (eff256 >= 0.9 || (rounds == 1 && eff256 >= 0.7))) cfg = 8;
+      // plain-epilogue GEMMs with many 256x256 tiles or a long K (the frozen ViT's qkv / fc1 / fc2): four waves of 128x128 with the
+      // hand-pipelined K loop (cfg 13) - 10-20 % faster than every other form standalone, ~1 ms per step in the train step
+      // (round 3: also the ViT proj, 366 tiles of K = 1408 — it ran on the generic 128x128 tile until then: 71.95 -> 71.43 ms per step)
+      static const bool no13 = mrb_env_present("MRB_NO_CFG13");
+      if (!no13 && !gated && !a.Aext && !a.out2 && !has_drop && (act == 0 || act == 1) && M >= 4096 && (t256 >= 2 * ncu || (t256 >= ncu && K >= 1024)))
+        cfg = 13;
+      // (256x128 with 16 waves, cfg 10, is 5-15 % faster than 128x128 at the ViT qkv shape standalone, but in the step it made things
+      // worse: one more persistent 16-wave block per CU starves the small kernels of the clip that shares the GPU with the look-ahead)
+      if (cfg != 0) {
+      } else if (t128 >= 400) cfg = 2;
+      else if (t64x128 >= 400 || gated) cfg = 4;
+      else cfg = 5;
+    }
+  }
+  if (a.t_inner > 0 || a.ext_group_n > 0) {   // the extras live in the generic tile kernel's staging / epilogue; the transposed copies need 64-column wave slabs
+    if (a.t_inner > 0 && cfg == 5) cfg = 4;
+    if (cfg == 13 || (cfg == 3 && q.requested == 0)) cfg = (M >= 1024 && N >= 1024) ? 2 : 4;
+    MRB_REQUIRE(cfg == 1 || cfg == 2 || cfg == 4 || cfg == 7 || cfg == 8 || cfg == 9 || cfg == 11 || (cfg >= 18 && cfg <= 21) || (a.t_inner == 0 && (cfg == 5 || cfg == 10 || cfg == 12)),
+                "gemm: head-transposed copies / grouped K extension are not available in tile config %d", cfg);
+  }
+  MRB_REQUIRE(!a.th_flags || !(cfg == 3 || (cfg >= 13 && cfg <= 17)), "gemm: the thin role lives in the generic tile kernel (tile config %d has none)", cfg);
+  if (act == 2) {   // the GELU-backward epilogue lives in the generic tile kernel's non-gated store path
+    if (cfg == 3 || cfg == 8 || (cfg >= 13 && cfg <= 17)) cfg = (M >= 1024 && N >= 1024) ? 4 : 5;
+    MRB_REQUIRE(cfg == 2 || cfg == 4 || cfg == 5 || (cfg >= 18 && cfg <= 23), "gemm: act 2 (GELU backward) is not available in tile config %d", cfg);
+  }
+  // an automatic cfg 13 on bf16 operands runs with three W stages (cfg 17: see launch_w4_cfg) unless MRB_W4_W3=0
+  if (cfg == 13 && !f16 && q.requested == 0) {
+    static const bool w3 = mrb_env_not_off("MRB_W4_W3");
+    if (w3) cfg = 17;
+  }
+  return MRBLIP_OK;
+}
+
+// Part 3 of gemm_dispatch: one line per tile config
+static int launch_cfg(GemmArgs& a, const GemmCall& q, int cfg) {
+  switch (cfg) {
+    case 3: return launch_skinny(a, q);
+    case 1: return launch_tile_cfg<true, 256, 256, 2, 4>(a, q);
+    case 6: return launch_tile_cfg<false, 256, 256, 2, 2>(a, q, "gemm: the 4-wave 256x256 tile has no gated epilogue");
+    case 7: return launch_tile_cfg<true, 256, 128, 2, 2, 32, 3>(a, q);   // 256x128 tile, 4 waves of 128x64, BK = 32, 3-stage ring (72 KB): two blocks per CU at 0.75 KB of LDS reads per MFMA
+    case 8: return launch_tile_cfg<true, 256, 256, 4, 4>(a, q);          // 256x256, 16 waves of 64x64 (4 waves per SIMD), one persistent block per CU
+    case 9: return launch_tile_cfg<true, 128, 128, 4, 2>(a, q);          // 128x128 with 8 waves of 32x64, two blocks per CU (4 waves per SIMD): measured = cfg 2, not auto-selected
+    case 10: return launch_tile_cfg<false, 256, 128, 4, 4>(a, q, "gemm: cfg 10 has no gated epilogue");   // 256x128, 16 waves of 64x32, one persistent block per CU
+    case 11: return launch_tile_cfg<false, 128, 256, 4, 4>(a, q, "gemm: cfg 11 has no gated epilogue");   // 128x256, 16 waves of 32x64 (measured <= cfg 10, not auto-selected)
+    case 12: return launch_tile_cfg<false, 256, 192, 4, 2>(a, q, "gemm: cfg 12 has no gated epilogue");   // 256x192, 8 waves of 64x96, one persistent block per CU: N = 1408 (ViT proj / fc2) is 7.3 x 192 -> 488 tiles = 1.9 rounds
+    case 13: case 14: case 17: return launch_w4_cfg(a, q, cfg);
+    case 15: return launch_w4d_cfg(a, q);
+    case 16: return launch_w16_cfg(a, q);
+    // (round 3, measured at the T5 [2012 x 2048] outputs and removed again: 128x128 tiles — one per CU, 2/3 of the L2->LDS traffic of
+    // 64x128 — with a 3- or 4-stage ring, or with 8 waves of 64x32: K = 10240: 115.9 / 114.6 / 112.5 us against 120.6 us for the plain
+    // 128x128 and 105.1 us for 64x128 at two blocks per CU; profiles/r03_gemm_t5_tiles.txt)
+    // deeper rings of the small tiles: with weights that come from HBM (every layer's own, not the re-used panel of a stand-alone loop) one
+    // K-tile of prefetch distance (0.5 us) is shorter than the memory latency
+    case 18: return launch_tile_cfg<true, 64, 128, 2, 2, 64, 3>(a, q);    // 64x128, 3 stages (72 KB: still two blocks per CU)
+    case 19: return launch_tile_cfg<true, 64, 128, 2, 2, 64, 4>(a, q);    // 64x128, 4 stages (96 KB: one block per CU)
+    case 20: return launch_tile_cfg<true, 128, 128, 2, 2, 64, 3>(a, q);   // 128x128, 3 stages (96 KB)
+    case 21: return launch_tile_cfg<true, 128, 128, 2, 2, 64, 4>(a, q);   // 128x128, 4 stages (128 KB)
+    // round 6: the same for the 64x64 tile (the Q-Former's M = 1920 products over K = 768: twelve K-tiles, each a full LDS-DMA latency with two stages)
+    case 22: return launch_tile_cfg<false, 64, 64, 2, 2, 64, 3>(a, q, "gemm: the 64x64 tile has no gated epilogue");   // 64x64, 3 stages (48 KB: three blocks per CU)
+    case 23: return launch_tile_cfg<false, 64, 64, 2, 2, 64, 4>(a, q, "gemm: the 64x64 tile has no gated epilogue");   // 64x64, 4 stages (64 KB: two blocks per CU)
+    case 4: return launch_tile_cfg<true, 64, 128, 2, 2>(a, q);
+    case 5: return launch_tile_cfg<false, 64, 64, 2, 2>(a, q, "gemm: the 64x64 tile has no gated epilogue");
+    default: return launch_tile_cfg<true, 128, 128, 2, 2>(a, q);   // cfg 2, and every number that names no config
+  }
+}
+
+// shared by the C entry points: (1) the calling thread's one-shots, validation, GemmArgs; (2) select_cfg; (3) launch_cfg.
+// ext_first / ext_* / a_* : see GemmArgs.
 static int gemm_dispatch(const void* A, long long lda, const void* W, long long ldw, const void* Aext, long long ldaext,
                          const void* Wext, long long ldwext, int M, int N, int K, void* out, long long ldo, int out_f32,
                          void* out2, long long ldo2, const float* bias, const float* residual, long long ldr, int act,
@@ -1969,7 +2192,6 @@ static int gemm_dispatch(const void* A, long long lda, const void* W, long long 
     mk_drop_arg(a.th_drop, seed_ptr, th.site, th.p);
   }
   a.pf_ptr = pf.ptr; a.pf_n16 = pf.bytes / 16; a.pf_ptr2 = pf.ptr2; a.pf_n16_2 = pf.bytes2 / 16; a.pf_blocks = pf.n_blocks;
-  const bool has_extra = a.t_inner > 0 || a.ext_group_n > 0;
   MRB_REQUIRE(a.t_inner == 0 || (!out_f32 && !gated && act == 0 && !(p_drop > 0.f) && !residual && !out2 && (M == a.t_rows || (a.t_rows % 32) == 0) && (M % a.t_rows) == 0),
               "gemm: head-transposed copies need a bf16 output with a plain / bias epilogue and one clip or t_rows %% 32 == 0");
   MRB_REQUIRE(a.ext_group_n == 0 || (Aext && !gated && (N % a.ext_group_n) == 0 && ldaext >= (long long)(N / a.ext_group_n) * 64), "gemm: ext_group_n needs a K extension with one 64-column slot per group");
@@ -1986,331 +2208,10 @@ static int gemm_dispatch(const void* A, long long lda, const void* W, long long 
   a.drop.thresh24 = (uint32_t)(p_drop * 65536.0f + 0.5f);
   a.drop.inv_keep = 1.0f / (1.0f - p_drop);
   MRB_REQUIRE(!(p_drop > 0.f) || seed_ptr, "gemm: dropout needs a device seed pointer");
-  // tile_cfg: 0 auto, 1 = 256x256 (8 waves, persistent), 2 = 128x128, 3 = skinny, 4 = 64x128, 5 = 64x64, 8 = 256x256 with 16 waves,
-  // 13 = 256x256 with 4 waves (plain epilogues); measured and not auto-selected:
-  // 6 = 256x256 with 4 waves of 128x128 (1 wave/SIMD: 0.7x), 7 = 256x128 BK=32 3-stage (= 128x128), [128x128 BK=32 at 3-4 blocks/CU: 0.8x,
-  // 256x128 / 128x256 BK=64 with one 4-wave block per CU: 0.6x; 256x128 / 128x256 BK=32 with 8 waves of 64x64, two blocks per CU: 0.7x]
-  const int reserve_arg = (tile_cfg >> 8) & 0x1ff;   // per-call CU reserve (see mrblip_gemm_set_cu_reserve)
-  const int k_splits = (tile_cfg >> 17) & 0xf;        // skinny kernel: K split with atomic accumulation into a pre-initialised fp32 output
-  int cfg = tile_cfg & 0xff;
-  if (f16) {   // IEEE fp16 operands: the frozen ViT's GEMMs, which all take the 4-wave 256x256 kernel with a plain epilogue
-    MRB_REQUIRE(cfg == 0 || cfg == 13, "gemm_f16: only the 4-wave 256x256 kernel (tile_cfg 0 / 13) has an fp16 form");
-    cfg = 13;
-  }
-  if (cfg == 0) {
-    if (M <= 64 && !gated) cfg = 3;
-    else {
-      // measured on MI355X (tools/gemm_bench.py, tools/gemm_kfit.py): the 256x256 kernel (1 block/CU) only wins for long-K, many-tile
-      // problems; 128x128 (2 blocks/CU hide each other's staging latency and epilogue) wins at the ViT shapes; outputs with fewer
-      // 128x128 tiles than resident block slots (T5 [2012,2048], Q-Former [1920,768]) are tile-starved -> 64x128 / 64x64 tiles.
-      const int ncols = gated ? N / 2 : N;
-      const long long t256 = (long long)((M + 255) / 256) * ((ncols + (gated ? 127 : 255)) / (gated ? 128 : 256));
-      const long long t128 = (long long)((M + 127) / 128) * ((ncols + (gated ? 63 : 127)) / (gated ? 64 : 128));
-      const long long t64x128 = (long long)((M + 63) / 64) * ((ncols + (gated ? 63 : 127)) / (gated ? 64 : 128));
-      // 256x256 with 16 waves of 64x64 (4 waves per SIMD hide each other's LDS-DMA issue; half the L2->LDS bytes per flop of 128x128)
-      // is the fastest main loop, but it runs one block per CU: it pays only when its rounds are full (ViT fc1: 1464 tiles = 5.7
-      // rounds of 256 CUs) or when one partial round covers most CUs (T5 qkv: 192 tiles)
-      static int ncu = 0;
-      if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-      }
-      const long long rounds = (t256 + ncu - 1) / ncu;
-      const double eff256 = (double)t256 / (double)(rounds * ncu);
-      static int no8 = -1;
-      if (no8 < 0) no8 = getenv("MRB_NO_CFG8") ? 1 : 0;
-      if (!no8 && !gated && K >= 1024 && (eff256 >= 0.9 || (rounds == 1 && eff256 >= 0.7))) cfg = 8;
-      // plain-epilogue GEMMs with many 256x256 tiles or a long K (the frozen ViT's qkv / fc1 / fc2): four waves of 128x128 with the
-      // hand-pipelined K loop (cfg 13) - 10-20 % faster than every other form standalone, ~1 ms per step in the train step
-      // (round 3: also the ViT proj, 366 tiles of K = 1408 — it ran on the generic 128x128 tile until then: 71.95 -> 71.43 ms per step)
-      static int no13 = -1;
-      if (no13 < 0) no13 = getenv("MRB_NO_CFG13") ? 1 : 0;
-      if (!no13 && !gated && !Aext && !out2 && !(p_drop > 0.f) && (act == 0 || act == 1) && M >= 4096 && (t256 >= 2 * ncu || (t256 >= ncu && K >= 1024)))
-        cfg = 13;
-      // (256x128 with 16 waves, cfg 10, is 5-15 % faster than 128x128 at the ViT qkv shape standalone, but in the step it made things
-      // worse: one more persistent 16-wave block per CU starves the small kernels of the clip that shares the GPU with the look-ahead)
-      if (cfg != 0) {
-      } else if (t128 >= 400) cfg = 2;
-      else if (t64x128 >= 400 || gated) cfg = 4;
-      else cfg = 5;
-    }
-  }
-  if (has_extra) {   // the extras live in the generic tile kernel's staging / epilogue; the transposed copies need 64-column wave slabs
-    if (a.t_inner > 0 && cfg == 5) cfg = 4;
-    if (cfg == 13 || (cfg == 3 && (tile_cfg & 0xff) == 0)) cfg = (M >= 1024 && N >= 1024) ? 2 : 4;
-    MRB_REQUIRE(cfg == 1 || cfg == 2 || cfg == 4 || cfg == 7 || cfg == 8 || cfg == 9 || cfg == 11 || (cfg >= 18 && cfg <= 21) || (a.t_inner == 0 && (cfg == 5 || cfg == 10 || cfg == 12)),
-                "gemm: head-transposed copies / grouped K extension are not available in tile config %d", cfg);
-  }
-  MRB_REQUIRE(!a.th_flags || !(cfg == 3 || (cfg >= 13 && cfg <= 17)), "gemm: the thin role lives in the generic tile kernel (tile config %d has none)", cfg);
-  if (act == 2) {   // the GELU-backward epilogue lives in the generic tile kernel's non-gated store path
-    if (cfg == 3 || cfg == 8 || (cfg >= 13 && cfg <= 17)) cfg = (M >= 1024 && N >= 1024) ? 4 : 5;
-    MRB_REQUIRE(cfg == 2 || cfg == 4 || cfg == 5 || (cfg >= 18 && cfg <= 23), "gemm: act 2 (GELU backward) is not available in tile config %d", cfg);
-  }
-  if (cfg == 3) {
-    MRB_REQUIRE(!gated, "gemm: skinny kernel has no gated epilogue");
-    // rows of the tall operand per block: 32, fewer when the grid would leave most CUs idle (LoRA down / g products at M = 2012)
-    int rpb = 32;
-    static int rpb32 = -1;
-    if (rpb32 < 0) rpb32 = getenv("MRB_SKINNY_RPB32") ? 1 : 0;
-    while (!rpb32 && rpb > 8 && (long long)((N + 31) / 32) * ((M + rpb - 1) / rpb) < 192 && M > rpb) rpb >>= 1;
-    a.m_rows_per_block = rpb;
-    dim3 grid((N + 31) / 32, (M + rpb - 1) / rpb);
-    if (k_splits > 1) {
-      MRB_REQUIRE(out_f32 && !residual && !out2 && act == 0, "gemm: the K-split form adds into a pre-initialised fp32 output (no residual / out2 / act)");
-      a.k_splits = k_splits;
-      grid.z = k_splits;
-    }
-    // (a 16-wave K-split changes nothing here: with one lane per operand row these launches are bound by the number of row-gather
-    // load instructions one CU's address unit can retire, not by a wave's sequential load rounds)
-    // (measured and dropped for the tall-and-thin LoRA products of the encoder, M = 2012, N <= 32: one block per 32 rows with 16 waves
-    // splitting K - all lanes of every load and dropout hash valid, 4 waves per CU - 10.9 vs 12.4 us at K = 2048 but 38 vs 25 us at
-    // K = 10240, +0.4 ms per step: profiles/r02_skinny_tall16.txt)
-    if (out_f32) hipLaunchKernelGGL((gemm_skinny_kernel<true, 4>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((gemm_skinny_kernel<false, 4>), grid, dim3(256), 0, stream, a);
-    return mrblip_check_launch("gemm_skinny");
-  }
-  if (cfg == 1) {
-    if (gated) return launch_tile<256, 256, 2, 4, false, true>(a, stream);
-    return out_f32 ? launch_tile<256, 256, 2, 4, true, false>(a, stream) : launch_tile<256, 256, 2, 4, false, false>(a, stream);
-  }
-  if (cfg == 6) {
-    MRB_REQUIRE(!gated, "gemm: the 4-wave 256x256 tile has no gated epilogue");
-    return out_f32 ? launch_tile<256, 256, 2, 2, true, false>(a, stream) : launch_tile<256, 256, 2, 2, false, false>(a, stream);
-  }
-  if (cfg == 7) {  // 256x128 tile, 4 waves of 128x64, BK = 32, 3-stage ring (72 KB): two blocks per CU at 0.75 KB of LDS reads per MFMA
-    if (gated) return launch_tile<256, 128, 2, 2, false, true, 32, 3>(a, stream);
-    return out_f32 ? launch_tile<256, 128, 2, 2, true, false, 32, 3>(a, stream) : launch_tile<256, 128, 2, 2, false, false, 32, 3>(a, stream);
-  }
-  if (cfg == 8) {  // 256x256, 16 waves of 64x64 (4 waves per SIMD), one persistent block per CU
-    if (gated) return launch_tile<256, 256, 4, 4, false, true>(a, stream);
-    return out_f32 ? launch_tile<256, 256, 4, 4, true, false>(a, stream) : launch_tile<256, 256, 4, 4, false, false>(a, stream);
-  }
-  if (cfg == 9) {  // 128x128 with 8 waves of 32x64, two blocks per CU (4 waves per SIMD): measured = cfg 2, not auto-selected
-    if (gated) return launch_tile<128, 128, 4, 2, false, true>(a, stream);
-    return out_f32 ? launch_tile<128, 128, 4, 2, true, false>(a, stream) : launch_tile<128, 128, 4, 2, false, false>(a, stream);
-  }
-  if (cfg == 10) {  // 256x128, 16 waves of 64x32, one persistent block per CU
-    MRB_REQUIRE(!gated, "gemm: cfg 10 has no gated epilogue");
-    return out_f32 ? launch_tile<256, 128, 4, 4, true, false>(a, stream) : launch_tile<256, 128, 4, 4, false, false>(a, stream);
-  }
-  if (cfg == 11) {  // 128x256, 16 waves of 32x64 (measured <= cfg 10, not auto-selected)
-    MRB_REQUIRE(!gated, "gemm: cfg 11 has no gated epilogue");
-    return out_f32 ? launch_tile<128, 256, 4, 4, true, false>(a, stream) : launch_tile<128, 256, 4, 4, false, false>(a, stream);
-  }
-  if (cfg == 12) {  // 256x192, 8 waves of 64x96, one persistent block per CU: N = 1408 (ViT proj / fc2) is 7.3 x 192 -> 488 tiles = 1.9 rounds
-    MRB_REQUIRE(!gated, "gemm: cfg 12 has no gated epilogue");
-    return out_f32 ? launch_tile<256, 192, 4, 2, true, false>(a, stream) : launch_tile<256, 192, 4, 2, false, false>(a, stream);
-  }
-  if (cfg == 15) {  // cfg 13's tile with the deferred epilogue (bf16 out, bias, optional GELU, no residual): ViT qkv / fc1
-    MRB_REQUIRE(!gated && !Aext && !out2 && !(p_drop > 0.f) && !out_f32 && !residual && (act == 0 || act == 1), "gemm: cfg 15 = bf16 out, bias, optional GELU only");
-    a.tiles_m = (M + 255) / 256;
-    a.tiles_n = (N + 255) / 256;
-    const int LDS = 2 * (256 + 256) * 128;
-    static int ncu15 = 0;
-    if (ncu15 == 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      ncu15 = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    const int nt15 = a.tiles_m * a.tiles_n;
-    const int reserve = reserve_arg ? reserve_arg / 8 * 8 : g_cu_reserve;
-    const int cus = ncu15 - reserve > 8 ? ncu15 - reserve : 8;
-    const int grid = nt15 < cus ? (nt15 + 7) / 8 * 8 : cus;
-    static bool attr15[2] = {};
-    if (act == 1) {
-      auto k = gemm_w4d_kernel<1>;
-      if (!attr15[1]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) { mrblip_set_error("gemm: cannot raise dynamic LDS to %d", LDS); return MRBLIP_ELAUNCH; }
-        attr15[1] = true;
-      }
-      hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, stream, a);
-    } else {
-      auto k = gemm_w4d_kernel<0>;
-      if (!attr15[0]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) { mrblip_set_error("gemm: cannot raise dynamic LDS to %d", LDS); return MRBLIP_ELAUNCH; }
-        attr15[0] = true;
-      }
-      hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, stream, a);
-    }
-    return mrblip_check_launch("gemm_w4d");
-  }
-  if (cfg == 16) {  // cfg 13's tile on 16x16x32 MFMAs
-    MRB_REQUIRE(!gated && !Aext && !out2 && !(p_drop > 0.f) && (act == 0 || act == 1), "gemm: cfg 16 takes plain epilogues only");
-    a.tiles_m = (M + 255) / 256;
-    a.tiles_n = (N + 255) / 256;
-    const int LDS = 2 * (256 + 256) * 128;
-    static int ncu16 = 0;
-    if (ncu16 == 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      ncu16 = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    const int nt16 = a.tiles_m * a.tiles_n;
-    const int reserve = reserve_arg ? reserve_arg / 8 * 8 : g_cu_reserve;
-    const int cus = ncu16 - reserve > 8 ? ncu16 - reserve : 8;
-    const int grid = nt16 < cus ? (nt16 + 7) / 8 * 8 : cus;
-    const int variant = (out_f32 ? 4 : 0) | (act == 1 ? 2 : 0) | (residual ? 1 : 0);
-    static bool attr_set16[8] = {};
-#define MRB_W16_LAUNCH(V, F32, ACT_, RES_)                                                                                         \
-  case V: {                                                                                                                        \
-    auto k = gemm_w16_kernel<F32, ACT_, RES_>;                                                                                     \
-    if (!attr_set16[V]) {                                                                                                          \
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {                    \
-        mrblip_set_error("gemm: cannot raise dynamic LDS to %d", LDS);                                                             \
-        return MRBLIP_ELAUNCH;                                                                                                     \
-      }                                                                                                                            \
-      attr_set16[V] = true;                                                                                                        \
-    }                                                                                                                              \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, stream, a);                                                                  \
-    break;                                                                                                                         \
-  }
-    switch (variant) {
-      MRB_W16_LAUNCH(0, false, 0, false)
-      MRB_W16_LAUNCH(1, false, 0, true)
-      MRB_W16_LAUNCH(2, false, 1, false)
-      MRB_W16_LAUNCH(3, false, 1, true)
-      MRB_W16_LAUNCH(4, true, 0, false)
-      MRB_W16_LAUNCH(5, true, 0, true)
-      MRB_W16_LAUNCH(6, true, 1, false)
-      MRB_W16_LAUNCH(7, true, 1, true)
-    }
-#undef MRB_W16_LAUNCH
-    return mrblip_check_launch("gemm_w16");
-  }
-  // cfg 17 (round 4): cfg 13 with a third stage buffer for the W operand (gemm_w4_kernel W3).  Measured (profiles/r04_w3_bench.txt):
-  // bit-identical; with the chip to itself equal within noise (8192^3 1426 vs 1426 TFLOP/s, fc1 252.5 vs 250.5 us, fc2 298 vs 303 us);
-  // on the 192 CUs the look-ahead runs on: 8192^3 1217 vs 1140 TFLOP/s, fc2 280 vs 285 us, fc1 in the step 340 vs 348 us; step 70.48 vs
-  // 70.45 ms.  So the late W pieces were NOT what the K loop waits for; the form is kept as the library's choice for an automatic cfg 13
-  // because it is never slower where it runs (MRB_W4_W3=0: two stages; an explicit tile_cfg 13 always means two stages)
-  bool w3 = cfg == 17;
-  if (cfg == 13 && !f16 && (tile_cfg & 0xff) == 0) {
-    static int w3env = -1;
-    if (w3env < 0) { const char* e = getenv("MRB_W4_W3"); w3env = (e && e[0] == '0') ? 0 : 1; }
-    w3 = w3env == 1;
-  }
-  if (cfg == 17) cfg = 13;
-  if (cfg == 13 || cfg == 14) {  // four waves of 128 x 128 (cfg 13, 256x256 tile) / 128 x 96 (cfg 14, 256x192), hand-pipelined K loop
-    MRB_REQUIRE(gated || (!Aext && !out2 && !(p_drop > 0.f)), "gemm: cfg 13 / 14 take plain epilogues only (or the gated-GELU form of cfg 13)");
-    MRB_REQUIRE(!gated || (cfg == 13 && !Aext && !f16 && (N % 16) == 0 && (!out2 || (long long)M * ldo2 * 2 < (1ll << 31))),
-                "gemm: the gated form of the 4-wave kernel is cfg 13 on bf16 operands without a K extension ([x | u] x [W | B]^T instead)");
-    MRB_REQUIRE(act == 0 || act == 1, "gemm: cfg 13 / 14 know act 0 / 1");
-    MRB_REQUIRE((long long)M * ldo * (out_f32 ? 4 : 2) < (1ll << 31) && (!residual || (long long)M * ldr * 4 < (1ll << 31)),
-                "gemm: cfg 13 / 14 address output and residual through 2 GiB buffer resources");
-    const int bn13 = cfg == 13 ? 256 : 192;
-    a.tiles_m = (M + 255) / 256;
-    a.tiles_n = gated ? (N / 2 + 127) / 128 : (N + bn13 - 1) / bn13;      // (gated: 128 output columns per tile)
-    if (gated) w3 = false;
-    const int stage13 = (256 + bn13) * 128, slab13 = 4 * 32 * (bn13 / 2 * 4 + 16);
-    MRB_REQUIRE(!w3 || (cfg == 13 && !f16), "gemm: the three-W-stage form (cfg 17) exists for the bf16 256x256 tile");
-    const int LDS = w3 ? 2 * stage13 + 256 * 128 : (2 * stage13 > stage13 + slab13 ? 2 * stage13 : stage13 + slab13);
-    static int ncu13 = 0;
-    if (ncu13 == 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      ncu13 = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    const int nt13 = a.tiles_m * a.tiles_n;
-    // g_cu_reserve: CUs this persistent kernel leaves alone (mrblip_gemm_set_cu_reserve).  Its blocks hold a whole CU each for the
-    // whole launch (all 512 registers of every SIMD), so kernels of another stream can only start on CUs it does not occupy: the
-    // frozen-ViT look-ahead of the train step gives the clip that is being trained a quarter of the chip this way.
-    const int reserve = reserve_arg ? reserve_arg / 8 * 8 : g_cu_reserve;
-    const int cus = ncu13 - reserve > 8 ? ncu13 - reserve : 8;
-    // (a multiple of 8: the same number of blocks on every XCD.  Measured and dropped in round 3: shrinking the grid to the fewest CUs
-    // that keep the round count — ceil(tiles / rounds): ViT fc1 1464 tiles = 8 rounds on 184 CUs as on 192 — so that the other stream
-    // gets the difference: +0.3 ms per step; the CUs of a partly filled last round are not idle, they go to the other stream EARLIER.)
-    const int grid = nt13 < cus ? (nt13 + 7) / 8 * 8 : cus;
-    const int variant = gated ? 32 : (w3 ? 24 : 0) + ((f16 ? 16 : 0) | (cfg == 14 ? 8 : 0) | (out_f32 ? 4 : 0) | (act == 1 ? 2 : 0) | (residual ? 1 : 0));
-    static bool attr_set13[33] = {};
-#define MRB_W4_LAUNCH(V, F32, ACT_, RES_, TN_, ...)                                                                                \
-  case V: {                                                                                                                        \
-    auto k = gemm_w4_kernel<F32, ACT_, RES_, TN_, ##__VA_ARGS__>;                                                                                 \
-    if (!attr_set13[V]) {                                                                                                          \
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {                    \
-        mrblip_set_error("gemm: cannot raise dynamic LDS to %d", LDS);                                                             \
-        return MRBLIP_ELAUNCH;                                                                                                     \
-      }                                                                                                                            \
-      attr_set13[V] = true;                                                                                                        \
-    }                                                                                                                              \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, stream, a);                                                                  \
-    break;                                                                                                                         \
-  }
-    switch (variant) {
-      MRB_W4_LAUNCH(0, false, 0, false, 4)
-      MRB_W4_LAUNCH(1, false, 0, true, 4)
-      MRB_W4_LAUNCH(2, false, 1, false, 4)
-      MRB_W4_LAUNCH(3, false, 1, true, 4)
-      MRB_W4_LAUNCH(4, true, 0, false, 4)
-      MRB_W4_LAUNCH(5, true, 0, true, 4)
-      MRB_W4_LAUNCH(6, true, 1, false, 4)
-      MRB_W4_LAUNCH(7, true, 1, true, 4)
-      MRB_W4_LAUNCH(8, false, 0, false, 3)
-      MRB_W4_LAUNCH(9, false, 0, true, 3)
-      MRB_W4_LAUNCH(10, false, 1, false, 3)
-      MRB_W4_LAUNCH(11, false, 1, true, 3)
-      MRB_W4_LAUNCH(12, true, 0, false, 3)
-      MRB_W4_LAUNCH(13, true, 0, true, 3)
-      MRB_W4_LAUNCH(14, true, 1, false, 3)
-      MRB_W4_LAUNCH(15, true, 1, true, 3)
-      // fp16 operands (ViT): qkv (bf16-sized out + bias), fc1 (+ GELU), proj / fc2 (fp32 residual stream), patch embedding (fp32 out + bias)
-      MRB_W4_LAUNCH(16, false, 0, false, 4, true)
-      MRB_W4_LAUNCH(18, false, 1, false, 4, true)
-      MRB_W4_LAUNCH(20, true, 0, false, 4, true)
-      MRB_W4_LAUNCH(21, true, 0, true, 4, true)
-      // three W stages (cfg 17): the frozen ViT's four bf16 forms
-      MRB_W4_LAUNCH(24, false, 0, false, 4, false, true)
-      MRB_W4_LAUNCH(26, false, 1, false, 4, false, true)
-      MRB_W4_LAUNCH(28, true, 0, false, 4, false, true)
-      MRB_W4_LAUNCH(29, true, 0, true, 4, false, true)
-      // gated-GELU (T5 wi_0 / wi_1): bf16 y + bf16 pre-activations, dropout
-      MRB_W4_LAUNCH(32, false, 0, false, 4, false, false, false, true)
-      default:
-        mrblip_set_error("gemm: no such 4-wave kernel variant (%d)%s", variant, f16 ? " - the fp16 form exists for bias / bias+GELU (16-bit out) and fp32 out with or without residual" : "");
-        return MRBLIP_EINVAL;
-    }
-#undef MRB_W4_LAUNCH
-    return mrblip_check_launch("gemm_w4");
-  }
-  // (round 3, measured at the T5 [2012 x 2048] outputs and removed again: 128x128 tiles — one per CU, 2/3 of the L2->LDS traffic of
-  // 64x128 — with a 3- or 4-stage ring, or with 8 waves of 64x32: K = 10240: 115.9 / 114.6 / 112.5 us against 120.6 us for the plain
-  // 128x128 and 105.1 us for 64x128 at two blocks per CU; profiles/r03_gemm_t5_tiles.txt)
-  // deeper rings of the small tiles: with weights that come from HBM (every layer's own, not the re-used panel of a stand-alone loop) one
-  // K-tile of prefetch distance (0.5 us) is shorter than the memory latency
-  if (cfg == 18) {  // 64x128, 3 stages (72 KB: still two blocks per CU)
-    if (gated) return launch_tile<64, 128, 2, 2, false, true, 64, 3>(a, stream);
-    return out_f32 ? launch_tile<64, 128, 2, 2, true, false, 64, 3>(a, stream) : launch_tile<64, 128, 2, 2, false, false, 64, 3>(a, stream);
-  }
-  if (cfg == 19) {  // 64x128, 4 stages (96 KB: one block per CU)
-    if (gated) return launch_tile<64, 128, 2, 2, false, true, 64, 4>(a, stream);
-    return out_f32 ? launch_tile<64, 128, 2, 2, true, false, 64, 4>(a, stream) : launch_tile<64, 128, 2, 2, false, false, 64, 4>(a, stream);
-  }
-  if (cfg == 20) {  // 128x128, 3 stages (96 KB)
-    if (gated) return launch_tile<128, 128, 2, 2, false, true, 64, 3>(a, stream);
-    return out_f32 ? launch_tile<128, 128, 2, 2, true, false, 64, 3>(a, stream) : launch_tile<128, 128, 2, 2, false, false, 64, 3>(a, stream);
-  }
-  if (cfg == 21) {  // 128x128, 4 stages (128 KB)
-    if (gated) return launch_tile<128, 128, 2, 2, false, true, 64, 4>(a, stream);
-    return out_f32 ? launch_tile<128, 128, 2, 2, true, false, 64, 4>(a, stream) : launch_tile<128, 128, 2, 2, false, false, 64, 4>(a, stream);
-  }
-  // round 6: the same for the 64x64 tile (the Q-Former's M = 1920 products over K = 768: twelve K-tiles, each a full LDS-DMA latency with two stages)
-  if (cfg == 22) {  // 64x64, 3 stages (48 KB: three blocks per CU)
-    MRB_REQUIRE(!gated, "gemm: the 64x64 tile has no gated epilogue");
-    return out_f32 ? launch_tile<64, 64, 2, 2, true, false, 64, 3>(a, stream) : launch_tile<64, 64, 2, 2, false, false, 64, 3>(a, stream);
-  }
-  if (cfg == 23) {  // 64x64, 4 stages (64 KB: two blocks per CU)
-    MRB_REQUIRE(!gated, "gemm: the 64x64 tile has no gated epilogue");
-    return out_f32 ? launch_tile<64, 64, 2, 2, true, false, 64, 4>(a, stream) : launch_tile<64, 64, 2, 2, false, false, 64, 4>(a, stream);
-  }
-  if (cfg == 4) {
-    if (gated) return launch_tile<64, 128, 2, 2, false, true>(a, stream);
-    return out_f32 ? launch_tile<64, 128, 2, 2, true, false>(a, stream) : launch_tile<64, 128, 2, 2, false, false>(a, stream);
-  }
-  if (cfg == 5) {
-    MRB_REQUIRE(!gated, "gemm: the 64x64 tile has no gated epilogue");
-    return out_f32 ? launch_tile<64, 64, 2, 2, true, false>(a, stream) : launch_tile<64, 64, 2, 2, false, false>(a, stream);
-  }
-  if (gated) return launch_tile<128, 128, 2, 2, false, true>(a, stream);
-  return out_f32 ? launch_tile<128, 128, 2, 2, true, false>(a, stream) : launch_tile<128, 128, 2, 2, false, false>(a, stream);
+  const GemmCall q = {out_f32 != 0, gated != 0, f16, tile_cfg & 0xff, (tile_cfg >> 8) & 0x1ff, (tile_cfg >> 17) & 0xf, stream};
+  int cfg = 0;
+  if (int e = select_cfg(a, q, cfg)) return e;
+  return launch_cfg(a, q, cfg);
 }
 
 extern "C" int mrblip_gemm_bf16(const void* A, long long lda, const void* W, long long ldw, const void* Aext, long long ldaext,
@@ -2382,47 +2283,11 @@ extern "C" int mrblip_gemm_ksplit(const void* A, long long lda, const void* W, l
   a.tiles_m = (M + 255) / 256;
   a.tiles_n = (N + bn - 1) / bn;
   const int stage = (256 + bn) * 128, slab = 4 * 32 * (bn / 2 * 4 + 16);
-  static int w3s = -1;    // MRB_KSPLIT_W3=1: the 256x256 form with a third W stage (experiment; see cfg 17)
-  if (w3s < 0) { const char* e = getenv("MRB_KSPLIT_W3"); w3s = (e && e[0] == '1') ? 1 : 0; }
-  const bool w3 = w3s == 1 && cfg == 13;
+  static const bool w3s = mrb_env_on("MRB_KSPLIT_W3");    // MRB_KSPLIT_W3=1: the 256x256 form with a third W stage (experiment; see cfg 17)
+  const bool w3 = w3s && cfg == 13;
   const int LDS = w3 ? 2 * stage + 256 * 128 : (2 * stage > stage + slab ? 2 * stage : stage + slab);
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  const int units = a.tiles_m * a.tiles_n * parts;
-  const int reserve = ((tile_cfg >> 8) & 0x1ff) ? ((tile_cfg >> 8) & 0x1ff) / 8 * 8 : g_cu_reserve;
-  const int cus = ncu - reserve > 8 ? ncu - reserve : 8;
-  const int grid = units < cus ? (units + 7) / 8 * 8 : cus;
-  const int variant = w3 ? 6 + (out_f32 ? 1 : 0) : ((cfg == 14 ? 2 : cfg == 22 ? 4 : 0) | (out_f32 ? 1 : 0));
-  static bool attr_set[8] = {};
-#define MRB_W4S_LAUNCH(V, F32, TN_, ...)                                                                                           \
-  case V: {                                                                                                                        \
-    auto k = gemm_w4_kernel<F32, 0, false, TN_, false, ##__VA_ARGS__>;                                                             \
-    if (!attr_set[V]) {                                                                                                            \
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {                    \
-        mrblip_set_error("gemm_ksplit: cannot raise dynamic LDS to %d", LDS);                                                      \
-        return MRBLIP_ELAUNCH;                                                                                                     \
-      }                                                                                                                            \
-      attr_set[V] = true;                                                                                                          \
-    }                                                                                                                              \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, stream, a);                                                                  \
-    break;                                                                                                                         \
-  }
-  switch (variant) {
-    MRB_W4S_LAUNCH(0, false, 4, false, true)
-    MRB_W4S_LAUNCH(1, true, 4, false, true)
-    MRB_W4S_LAUNCH(2, false, 3, false, true)
-    MRB_W4S_LAUNCH(3, true, 3, false, true)
-    MRB_W4S_LAUNCH(4, false, 2, false, true)
-    MRB_W4S_LAUNCH(5, true, 2, false, true)
-    MRB_W4S_LAUNCH(6, false, 4, true, true)
-    MRB_W4S_LAUNCH(7, true, 4, true, true)
-  }
-#undef MRB_W4S_LAUNCH
-  return mrblip_check_launch("gemm_ksplit");
+  const int grid = mrb_persistent_grid(a.tiles_m * a.tiles_n * parts, (tile_cfg >> 8) & 0x1ff);
+  return launch_w4("gemm_ksplit", a, w4_key(out_f32 != 0, 0, false, bn / 64, false, w3, true), grid, LDS, stream);
 }
 
 // ---- thin "TN" product for the LoRA weight gradients:  D[r, c] += sum_m U[m, r] * drop(Y)[m, c],  r < 32, contraction over the
@@ -2638,8 +2503,7 @@ __global__ __launch_bounds__(512) void lora_tn_multi_kernel(const TnMulti q) {
 // bound.  So: CT = 2 for batched launches whose every problem has a column count that is a multiple of 64, CT = 1 otherwise.
 // MRB_LORA_TN_CT = 1 / 2 forces one form for A/B (2 still needs the multiples of 64).
 static int tn_ct(const TnArgs* const* ps, int n, bool batched) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MRB_LORA_TN_CT"); env = e ? atoi(e) : 0; }
+  static const int env = mrb_env_int("MRB_LORA_TN_CT", 0);
   if (env == 1 || (env == 0 && !batched)) return 1;
   for (int i = 0; i < n; ++i)
     if (ps[i]->C % 64) return 1;

@@ -159,16 +159,6 @@ __global__ __launch_bounds__(256) void lora_rows_kernel(const LoraRowsArgs p) {
   }
 }
 
-static int lora_num_cu() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 // ---- the same product for TALL inputs (M >= LORA_THIN_MIN_M rows: the T5 encoder's M = 2012) on the matrix cores ------------------
 // Round 3: at M = 2012 the row kernel above is a chain of exposed latencies (stage A -> barrier -> a row's loads -> 32..96 KB of LDS
 // fragment reads per 4-KB row -> next row; 8-30 us per launch where the operand streams in 2-10 us, ~4.5 ms of main-stream time per step).
@@ -207,20 +197,12 @@ __global__ __launch_bounds__(512) void lora_thin_kernel(const LoraRowsArgs p) { 
 }
 
 static bool lora_thin_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("MRB_LORA_THIN");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  return on == 1;
+  static const bool on = mrb_env_not_off("MRB_LORA_THIN");
+  return on;
 }
 
 static int lora_thin_min_m() {   // rows from which the matrix-core thin kernel replaces the LDS-resident row kernel (MRB_LORA_THIN_MIN_M)
-  static int m = -1;
-  if (m < 0) {
-    const char* e = getenv("MRB_LORA_THIN_MIN_M");
-    m = e ? atoi(e) : LORA_THIN_MIN_M;
-  }
+  static const int m = mrb_env_int("MRB_LORA_THIN_MIN_M", LORA_THIN_MIN_M);
   return m;
 }
 
@@ -228,9 +210,8 @@ static int launch_thin(const LoraRowsArgs& a, hipStream_t st, int groups = 1) {
   // 8-row blocks (MRB_LORA_THIN_ROWS=8; M = 2012: 252 blocks instead of 126) are FASTER stand-alone (enc g wi 17.8 vs 21.1 us, g qkv 14.4 vs
   // 16.3) and SLOWER in the train step (71.95 vs 71.36 ms; row kernel: 72.55): the 126-block form leaves half of the CUs to the
   // gradient side stream and the look-ahead ViT that run beside it.  16 rows is the default.
-  static int rows8 = -1;
-  if (rows8 < 0) { const char* e = getenv("MRB_LORA_THIN_ROWS"); rows8 = (e && atoi(e) == 8) ? 1 : 0; }
-  const bool half = rows8 && groups == 1 && (a.M + 15) / 16 < lora_num_cu();
+  static const bool rows8 = mrb_env_equals("MRB_LORA_THIN_ROWS", 8);
+  const bool half = rows8 && groups == 1 && (a.M + 15) / 16 < mrb_num_cus();
   const dim3 grid(half ? (a.M + 7) / 8 : (a.M + 15) / 16, groups);
   if (a.R <= 16) {
     if (half) hipLaunchKernelGGL((lora_thin_kernel<1, 8, 8>), grid, dim3(512), 0, st, a);
@@ -247,30 +228,15 @@ static int launch_rows(const LoraRowsArgs& a, hipStream_t st) {
   const int kcw = a.K < LORA_KC ? a.K : LORA_KC;
   const int LDS = NR * 8 * kcw * 2;
   constexpr int LDS_MAX = NR * 8 * LORA_KC * 2;
-  const int ncu = lora_num_cu();
+  const int ncu = mrb_num_cus();
   // rows per wave.  One chunk: 1 (the blocks loop over their row groups, nothing is re-staged).  Several chunks: every block re-stages
   // all of A, so fewer, taller blocks — about one per CU.
   const int rpw = a.K <= LORA_KC ? 1 : (a.M <= 4 * ncu ? 1 : a.M <= 8 * ncu ? 2 : 4);
   const int nrg = (a.M + 4 * rpw - 1) / (4 * rpw);
   const int grid = a.K <= LORA_KC ? (nrg < ncu ? nrg : ncu) : nrg;
-  static bool attr[3] = {};
-#define MRB_LR_LAUNCH(I, RPW_)                                                                                                     \
-  {                                                                                                                                \
-    auto k = lora_rows_kernel<NR, RPW_>;                                                                                           \
-    if (!attr[I]) {                                                                                                                \
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) != hipSuccess) {                \
-        mrblip_set_error("lora_rows: cannot raise dynamic LDS to %d", LDS_MAX);                                                    \
-        return MRBLIP_ELAUNCH;                                                                                                     \
-      }                                                                                                                            \
-      attr[I] = true;                                                                                                              \
-    }                                                                                                                              \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, st, a);                                                                      \
-  }
-  if (rpw == 1) MRB_LR_LAUNCH(0, 1)
-  else if (rpw == 2) MRB_LR_LAUNCH(1, 2)
-  else MRB_LR_LAUNCH(2, 4)
-#undef MRB_LR_LAUNCH
-  return mrblip_check_launch("lora_rows");
+  if (rpw == 1) return mrb_launch_lds<lora_rows_kernel<NR, 1>>("lora_rows", LDS_MAX, dim3(grid), dim3(256), LDS, st, a);
+  if (rpw == 2) return mrb_launch_lds<lora_rows_kernel<NR, 2>>("lora_rows", LDS_MAX, dim3(grid), dim3(256), LDS, st, a);
+  return mrb_launch_lds<lora_rows_kernel<NR, 4>>("lora_rows", LDS_MAX, dim3(grid), dim3(256), LDS, st, a);
 }
 
 // U[M, 0:R] = dropout(X)[M, K] A[R, K]^T (bf16 in / out, fp32 accumulate).  p_drop = 0 (or seed_ptr NULL): no mask (the backward's g = dy B).
@@ -431,26 +397,11 @@ extern "C" int mrblip_rmsnorm_lora_fwd(const float* x, long long ldx, const floa
   a.drop.inv_keep = 1.0f / (1.0f - p_drop);
   const int LDS = R * D * 2;
   const int grid = (M + 3) / 4 < 256 ? (M + 3) / 4 : 256;  // every block stages the thin vectors once and walks its rows
-  static bool attr[5] = {};
-#define MRB_NL_LAUNCH(NR_)                                                                                                         \
-  case NR_: {                                                                                                                      \
-    auto k = rmsnorm_lora_kernel<NR_>;                                                                                             \
-    if (!attr[NR_]) {                                                                                                              \
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, NR_ * 8 * 2048 * 2) != hipSuccess) {      \
-        mrblip_set_error("rmsnorm_lora: cannot raise dynamic LDS");                                                               \
-        return MRBLIP_ELAUNCH;                                                                                                     \
-      }                                                                                                                            \
-      attr[NR_] = true;                                                                                                            \
-    }                                                                                                                              \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, stream, a);                                                                  \
-    break;                                                                                                                         \
+  const dim3 g(grid), b(256);
+  switch (R / 8) {   // (the limit: the kernel's NR * 8 rows of the widest D)
+    case 1: return mrb_launch_lds<rmsnorm_lora_kernel<1>>("rmsnorm_lora", 1 * 8 * 2048 * 2, g, b, LDS, stream, a);
+    case 2: return mrb_launch_lds<rmsnorm_lora_kernel<2>>("rmsnorm_lora", 2 * 8 * 2048 * 2, g, b, LDS, stream, a);
+    case 3: return mrb_launch_lds<rmsnorm_lora_kernel<3>>("rmsnorm_lora", 3 * 8 * 2048 * 2, g, b, LDS, stream, a);
+    default: return mrb_launch_lds<rmsnorm_lora_kernel<4>>("rmsnorm_lora", 4 * 8 * 2048 * 2, g, b, LDS, stream, a);
   }
-  switch (R / 8) {
-    MRB_NL_LAUNCH(1)
-    MRB_NL_LAUNCH(2)
-    MRB_NL_LAUNCH(3)
-    MRB_NL_LAUNCH(4)
-  }
-#undef MRB_NL_LAUNCH
-  return mrblip_check_launch("rmsnorm_lora");
 }

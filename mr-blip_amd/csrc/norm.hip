@@ -349,8 +349,7 @@ extern "C" int mrblip_layernorm_bwd(const float* dy, long long lddy, const float
                                     float* dbeta, hipStream_t stream) {
   if (int e = norm_check(M, D, x, ldx)) return e;
   // (dgamma / dbeta: at most NORM_DW_MAXB blocks, whose partial sums the last one adds in block order; MRB_NORM_DW_ATOMIC=1: fp32 atomics)
-  static int dw_atomic = -1;
-  if (dw_atomic < 0) { const char* e = getenv("MRB_NORM_DW_ATOMIC"); dw_atomic = (e && e[0] == '1') ? 1 : 0; }
+  static const bool dw_atomic = mrb_env_on("MRB_NORM_DW_ATOMIC");
   char* ws = (dgamma && !dw_atomic && ((uintptr_t)dgamma % 16) == 0 && (!dbeta || ((uintptr_t)dbeta % 16) == 0)) ? mrblip_reduce_workspace() : nullptr;
   const int ordered = ws ? 1 : 0;
   const int grid = min((M + 3) / 4, dgamma ? (ordered ? NORM_DW_MAXB : 512) : 2048);

@@ -638,15 +638,5 @@ extern "C" int mrblip_qformer_layer_fwd(const mrblip_qformer_layer* a, hipStream
   k.d_cattn = qf_drop(a->seed_ptr, a->site_cattn, a->p_drop); k.d_co = qf_drop(a->seed_ptr, a->site_co, a->p_drop);
   k.d_ffn = qf_drop(a->seed_ptr, a->site_ffn, a->p_drop);
   k.eps = a->eps;
-  // (idempotent; a thread-local "done" flag only skips the repeated driver call)
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(qformer_layer_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, qf::LDS_BYTES) != hipSuccess) {
-      mrblip_set_error("qformer_layer_fwd: cannot reserve %d bytes of LDS", qf::LDS_BYTES);
-      return MRBLIP_ELAUNCH;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(qformer_layer_fwd_kernel, dim3(a->F), dim3(256), qf::LDS_BYTES, stream, k);
-  return mrblip_check_launch("qformer_layer_fwd");
+  return mrb_launch_lds<qformer_layer_fwd_kernel>("qformer_layer_fwd", qf::LDS_BYTES, dim3(a->F), dim3(256), qf::LDS_BYTES, stream, k);
 }

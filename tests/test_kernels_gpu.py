@@ -37,7 +37,7 @@ def keep_mask(shape, seed, site, p):
     return dropout_keep(shape, seed, site, p).to(dev())
 
 
-@pytest.mark.parametrize("cfg", [1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14])
+@pytest.mark.parametrize("cfg", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 18, 19, 20, 21, 22, 23])
 @pytest.mark.parametrize("M,N,K", [(300, 264, 128), (64, 520, 192), (513, 1408, 576), (33, 264, 2304), (1, 8, 64), (257, 8, 128)])
 def test_gemm_plain(ops, cfg, M, N, K):
     torch.manual_seed(0)
@@ -51,7 +51,7 @@ def test_gemm_plain(ops, cfg, M, N, K):
         assert rel(out.float(), ref) < tol, (cfg, dt)
 
 
-@pytest.mark.parametrize("cfg", [1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12])
+@pytest.mark.parametrize("cfg", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 18, 19, 20, 21])
 def test_gemm_epilogues(ops, cfg):
     torch.manual_seed(1)
     M, N, K = 200, 328, 256
@@ -186,7 +186,7 @@ def test_gemm_cu_reserve_keeps_results(ops, cfg):
     assert torch.equal(out, ref)
 
 
-@pytest.mark.parametrize("cfg", [1, 2, 4, 7, 8, 9])
+@pytest.mark.parametrize("cfg", [1, 2, 4, 7, 8, 9, 18, 19, 20, 21])
 def test_gemm_gated(ops, cfg):
     torch.manual_seed(2)
     M, Nh, K = 300, 200, 128
@@ -208,6 +208,17 @@ def test_gemm_gated(ops, cfg):
     hh = h.float().requires_grad_(True)
     (torch.nn.functional.gelu(hh[:, :Nh]) * hh[:, Nh:] * mask / 0.9 * dy.float()).sum().backward()
     assert rel(dh.float(), hh.grad) < 4e-3
+
+
+@pytest.mark.parametrize("cfg,msg", [(5, "gemm: the 64x64 tile has no gated epilogue"), (10, "gemm: cfg 10 has no gated epilogue"),
+                                     (22, "gemm: the 64x64 tile has no gated epilogue")])
+def test_gemm_gated_rejected_by_tiles_without_a_gated_form(ops, cfg, msg):
+    a = bf(torch.randn(64, 64, device=dev()))
+    w = bf(torch.randn(32, 64, device=dev()))
+    y = torch.empty(64, 16, dtype=torch.bfloat16, device=dev())
+    with pytest.raises(ops.MrblipError) as err:
+        ops.gemm(a, w, y, gated=True, tile_cfg=cfg)
+    assert msg in str(err.value)
 
 
 @pytest.mark.parametrize("D", [1408, 768, 2048, 96])
