@@ -417,6 +417,25 @@ int mrblip_beam_finalize(const int* seq, long long lds, const float* beam_scores
  * [2, layers, R, Lmax, inner] with planes = 2 * layers), parents read on the device: HF's _reorder_cache(beam_idx) without the host
  * (search.py:94-97).  src != dst, because parents repeat.  inner % 8 == 0; an index outside 0..R-1 copies the row itself. */
 int mrblip_kv_gather_rows(const void* src, void* dst, const int* parents, int planes, int R, int Lmax, int inner, int t, mrblip_stream_t stream);
+/* Single-query self-attention of one decoder layer against the row-major self-attention cache of an incremental decode (csrc/decode.hip):
+ * kv_src / kv_dst bf16 [2 (k, v), layers, R, Lmax, inner], inner = H * D.  One launch, a workgroup per (row r, head h), with
+ * p = parents ? parents[r] : r (an index outside 0..R-1 is treated as r):
+ *   1. re-order on read — with parents: kv_dst[{k, v}, layer, r, j, h, :] = kv_src[{k, v}, layer, p, j, h, :] for j < pos.  kv_dst is the
+ *      OTHER cache buffer (parents repeat): kv_src == kv_dst with parents is rejected.  Without parents the cache is used in place and
+ *      kv_src == kv_dst is required.
+ *   2. append — row pos of K and V in kv_dst <- columns [inner, 2 inner) and [2 inner, 3 inner) of qkv[r] (bf16 [R, ldq]).
+ *   3. attend — s_j = scale * q . k_j + lut[h * 257 + clamp(j - pos, -128, 128) + 128] for j = 0..pos (q = columns [h D, (h + 1) D) of
+ *      qkv[r]; lut fp32 [H, 257], prompt.bias_lut's form, the clamp is the kernel's); softmax in fp32; o = sum_j softmax(s)_j v_j ->
+ *      out[r, h D : (h + 1) D] as bf16 (out bf16 [R, ldo]).  K and V are read row-major from the cache: no transposed copy.
+ * Position: pos (host int, validated as 0 <= pos < Lmax), or *pos_dev when pos_dev != NULL (pos is then ignored).  In the device form a
+ * value outside 0..Lmax-1 makes every workgroup return before its first store: out and kv_dst keep their contents.  The kernel never
+ * writes pos_dev, parents, qkv or kv_src (other than through kv_dst == kv_src, row pos of this layer).  Nothing of another layer, and no
+ * position above pos, is touched.
+ * D a multiple of 8 up to 128, 0 <= layer < layers, Lmax <= 8192, ldq >= 3 inner, ldo >= inner, ldq and ldo multiples of 8; the cache, qkv
+ * and out 16-byte aligned.  No atomics and a fixed reduction order: two launches give the same bits. */
+int mrblip_decode_self_attention(const void* kv_src, void* kv_dst, const void* qkv, long long ldq, void* out, long long ldo, const float* lut,
+                                 const int* parents, const int* pos_dev, int pos, int layers, int layer, int R, int Lmax, int H, int D,
+                                 float scale, mrblip_stream_t stream);
 
 #ifdef __cplusplus
 }

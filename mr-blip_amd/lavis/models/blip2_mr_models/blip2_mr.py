@@ -308,6 +308,8 @@ class BLIP2_MR(BaseModel):
             seed=cfg.get("seed", None),  # None: the engine's dropout stream follows torch's seed = run.seed + rank (train.py setup_seeds)
         )
         model.generate_device_search = bool(cfg.get("generate_device_search", False))
+        model.generate_fused_decode = bool(cfg.get("generate_fused_decode", False))
+        model.generate_graph_decode = bool(cfg.get("generate_graph_decode", False))
         model.load_checkpoint_from_config(cfg)
         return model
 
@@ -347,10 +349,15 @@ class BLIP2_MR(BaseModel):
     # decoding step.  Opt-in (model config key of the same name); taken for beam searches of <= 16 beams with both caches on and
     # max_length < 128, every other call runs the host search as before.
     generate_device_search = False
+    # the self-attention block of every incremental decode step as one launch per layer (engine._t5_decode_step_fused, csrc/decode.hip):
+    # host search, sampling and device search alike.  Opt-in (model config key of the same name).
+    generate_fused_decode = False
+    # device search + fused decode only: the decoder part of every step after the first as a captured graph (engine.t5_decode_step_graph)
+    generate_graph_decode = False
     generate_poll_done = True    # device search: poll the done counter (two steps late) and stop early; False runs all max_length steps
     generate_trace = None        # a list: receives the HOST beam search's decision trace (search.beam_search's ``trace``), for tests
     generate_detail = None       # a list: receives the host search's ``detail`` (candidate indices, next score, score magnitude)
-    last_generate_stats = None   # device search: {"steps", "steps_after_done", "search_host_s"} of the last generate call
+    last_generate_stats = None   # device search: {"steps", "steps_after_done", "search_host_s", "graph_captures", "graph_replays"} of the last generate call
 
     def forward(self, samples):
         """samples: the reference's dict (blip2_mr.py:433-445).  Optional extra key ``next_video``: the NEXT batch's frames (the train
@@ -589,6 +596,8 @@ class BLIP2_MR(BaseModel):
                 # incremental decoding (HF use_cache=True): one new position per step against the self-attention K/V cache, which the
                 # search re-orders through `parents` (HF's _reorder_cache)
                 state = eng.t5_decode_begin(B * K, int(max_length) + 1)
+                if self.generate_fused_decode:
+                    state["fused"] = True
 
                 def step_fn(seqs, parents):
                     logits = eng.t5_decode_step(state, seqs[:, -1], parents, cross, B, mask_k)
@@ -640,14 +649,21 @@ class BLIP2_MR(BaseModel):
         else:
             search.reset()
         state = eng.t5_decode_begin(B * K, max_length + 1, alt_cache=True)
+        decode_step = eng.t5_decode_step
+        if self.generate_fused_decode:
+            state["fused"] = True
+            if self.generate_graph_decode:
+                decode_step = eng.t5_decode_step_graph
+        captures, replays = eng.dec_graph_captures, eng.dec_graph_replays
         for _ in range(max_length):
             if self.generate_poll_done and search.finished():
                 break
-            logits = eng.t5_decode_step(state, search.tokens, search.parents, cross, B, mask)
+            logits = decode_step(state, search.tokens, search.parents, cross, B, mask)
             search.step(logits)
             search.done_count_async()
         best = search.finalize()
-        self.last_generate_stats = {"steps": search.steps, "steps_after_done": search.steps_after_done(), "search_host_s": search.host_seconds}
+        self.last_generate_stats = {"steps": search.steps, "steps_after_done": search.steps_after_done(), "search_host_s": search.host_seconds,
+                                    "graph_captures": eng.dec_graph_captures - captures, "graph_replays": eng.dec_graph_replays - replays}
         return best
 
     _dev_search = None

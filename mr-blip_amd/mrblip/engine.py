@@ -1975,6 +1975,8 @@ class MrBlipEngine:
         inner = H * dk
         R, t, kv, Lmax = state["R"], state["t"], state["kv"], state["Lmax"]
         assert not self.training and tokens.numel() == R and t < Lmax
+        if state.get("fused"):
+            return self._t5_decode_step_fused(state, tokens, parents, cross_cache, cross_batch, kmask)
         if parents is not None and parents.is_cuda:
             assert parents.dtype == torch.int32 and parents.numel() == R and "kv_alt" in state, "device parents: int32 [R] and t5_decode_begin(alt_cache=True)"
             if t > 0:
@@ -2016,6 +2018,125 @@ class MrBlipEngine:
         self.lg_fwd(self.t5["lm"], nf, u["lm"], logits)
         state["t"] = t + 1
         return logits
+
+    # ---- opt-in (state["fused"]): the self-attention block of a decode step as ONE launch per layer (csrc/decode.hip) instead of the
+    # strided copy into the cache, the head_transpose of the whole V cache and the MFMA tile kernel on one query row — and, with device
+    # parents, instead of the kv_gather_rows pass over the complete cache: the kernel stores the rows it reads for the attention into the
+    # other cache buffer.  Nothing in these launches depends on the position through a shape, a stride or a pointer.
+    def _decode_fused_body(self, kv_src, kv_dst, tok32, parents, cross_cache, cross_batch: int, kmask, pos: Optional[int] = None, pos_dev=None):
+        """every launch of one fused decode step: tok32 / parents int32 on the device (parents None: cache in place, kv_dst is kv_src);
+        the position is ``pos`` or the device word ``pos_dev``.  Returns the logits workspace."""
+        c = self.cfg
+        d, H, dk, ff, V = c.d_model, c.t5_heads, c.d_kv, c.d_ff, c.vocab
+        inner = H * dk
+        R = kv_src.shape[2]
+        rows = self.ws.get("s_rows")
+        if rows is None or rows.numel() < R:
+            rows = self.ws["s_rows"] = torch.arange(max(R, 64), dtype=torch.int32, device=self.dev)
+        x = self.buf("s_x", (R, d), f32, zero=False)
+        ops.row_copy(self.emb, tok32, x, rows[:R])
+        xn = self.buf("s_xn", (R, pad64(d)), bf16)
+        u = {k: self.buf("s_u_" + k, (R, 64), bf16) for k in ("qkv", "o", "cq", "co", "wi", "wo", "lm")}
+        qkv = self.buf("s_qkv", (R, 3 * inner), bf16, zero=False)
+        o = self.buf("s_o", (R, pad64(inner)), bf16)
+        cq = self.buf("s_cq", (R, inner), bf16, zero=False)
+        co = self.buf("s_co", (R, pad64(inner)), bf16)
+        y = self.buf("s_y", (R, pad64(ff)), bf16)
+        xa, xb = self.buf("s_xa", (R, d), f32, zero=False), self.buf("s_xb", (R, d), f32, zero=False)
+        Bc = cross_batch
+        for i, L in enumerate(self.t5["dec"]):
+            self.norm_lg_fwd(x, L["ln0"], L["qkv"], xn, u["qkv"], qkv)
+            ops.decode_self_attention(kv_src, kv_dst, qkv, o, self.lut_dec, i, H, pos=pos, pos_dev=pos_dev, parents=parents, scale=1.0)
+            self.lg_fwd(L["o"], o, u["o"], xa, residual=x)
+            self.norm_lg_fwd(xa, L["ln1"], L["cq"], xn, u["cq"], cq)
+            ck4, vt_c = cross_cache[i]
+            ops.attention_fwd(self.v4(cq, Bc, R // Bc, H, dk), ck4, vt_c, self.v4(co, Bc, R // Bc, H, dk), None, scale=1.0, kmask=kmask)
+            self.lg_fwd(L["co"], co, u["co"], xb, residual=xa)
+            self.norm_lg_fwd(xb, L["ln2"], L["wi"], xn, u["wi"], y, gated=True, tile_cfg=2)
+            self.lg_fwd(L["wo"], y, u["wo"], x, residual=xb)
+        nf = self.buf("s_nf", (R, pad64(d)), bf16)
+        ops.rmsnorm_fwd(x, self.t5["dec_final"], c.t5_eps, out_bf16=nf)
+        logits = self.buf("s_logits", (R, V), f32, zero=False)
+        self.lg_fwd(self.t5["lm"], nf, u["lm"], logits)
+        return logits
+
+    def _decode_fused_buffers(self, state: dict, parents):
+        """(kv_src, kv_dst, parents for the kernel) of the next fused step; device parents swap the state's two cache buffers"""
+        R, t, kv = state["R"], state["t"], state["kv"]
+        if parents is not None and parents.is_cuda:
+            assert parents.dtype == torch.int32 and parents.numel() == R and "kv_alt" in state, "device parents: int32 [R] and t5_decode_begin(alt_cache=True)"
+            dst = state["kv_alt"]
+            state["kv"], state["kv_alt"] = dst, kv      # (every step, position 0 included: the direction of a step is its parity)
+            return kv, dst, parents
+        if parents is not None and t > 0 and not torch.equal(parents, torch.arange(R)):
+            kv[:, :, :, :t] = kv[:, :, :, :t].index_select(2, self.h2d(parents, torch.int64))
+        return kv, kv, None
+
+    def _t5_decode_step_fused(self, state: dict, tokens, parents, cross_cache, cross_batch: int, kmask):
+        src, dst, par = self._decode_fused_buffers(state, parents)
+        logits = self._decode_fused_body(src, dst, self.h2d(tokens.reshape(-1), torch.int32), par, cross_cache, cross_batch, kmask, pos=state["t"])
+        state["t"] += 1
+        return logits
+
+    # ---- opt-in: the fused step with DEVICE tokens / parents as a captured graph.  The position is a device word that the graph itself
+    # increments, so one graph per direction of the cache ping-pong serves every position of every later call with the same buffers.
+    _dec_graphs = None
+    dec_graph_captures = 0     # (counted per engine: the increments below bind instance attributes)
+    dec_graph_replays = 0
+
+    @torch.no_grad()
+    @_with_attention_split
+    def t5_decode_step_graph(self, state: dict, tokens: torch.Tensor, parents: torch.Tensor, cross_cache, cross_batch: int, kmask):
+        """t5_decode_step for a fused state and int32 device tokens / parents.  Position 0 of a decode runs eager (it creates every named
+        workspace and sets the position word); every later position is one replay of the graph of its direction, captured when first needed.
+        Key: (R, cross_batch, S, Lmax), the addresses of the cross cache, the mask, tokens, parents and of the step's own workspaces; a
+        mismatch captures anew, the oldest of more than ``graph_max_buckets`` keys is dropped."""
+        from collections import OrderedDict
+        R, t, Lmax = state["R"], state["t"], state["Lmax"]
+        assert not self.training and state.get("fused") and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.numel() == R and t < Lmax
+        pos_dev = self.buf("s_pos", (1,), torch.int32)
+        src, dst, par = self._decode_fused_buffers(state, parents)
+        tok32 = tokens.reshape(-1)
+        state["t"] = t + 1
+        if kmask is not None:      # (pad_mask builds a fresh tensor per call: the graphs read the key mask from a workspace of their own)
+            static_mask = self.buf("s_kmask", kmask.shape, kmask.dtype)
+            if t == 0:
+                static_mask.copy_(kmask)
+            kmask = static_mask
+        if t == 0:
+            pos_dev.zero_()
+            logits = self._decode_fused_body(src, dst, tok32, par, cross_cache, cross_batch, kmask, pos_dev=pos_dev)
+            pos_dev.add_(1)
+            state["graph_ptrs"] = tuple(self.ws[n].data_ptr() for n in sorted(self.ws) if n.startswith("s_") and torch.is_tensor(self.ws[n]))
+            return logits
+        S = int(cross_cache[0][0].shape[1])
+        key = (R, int(cross_batch), S, Lmax, tuple((k4.data_ptr(), vt.data_ptr()) for k4, vt in cross_cache),
+               None if kmask is None else kmask.data_ptr(), tok32.data_ptr(), par.data_ptr(), state["graph_ptrs"])   # (the s_* workspaces: s_kmask among them)
+        if self._dec_graphs is None:
+            self._dec_graphs = OrderedDict()
+        rec = self._dec_graphs.get(key)
+        if rec is None:
+            # (a workspace that grew has moved for good: keys holding its old address can never be met again and would only keep
+            # their graphs alive until the cap evicts them)
+            for stale in [k for k in self._dec_graphs if k[-1] != state["graph_ptrs"]]:
+                self._dec_graphs.pop(stale).clear()
+            rec = self._dec_graphs[key] = {}
+            while len(self._dec_graphs) > self.graph_max_buckets:
+                self._dec_graphs.popitem(last=False)[1].clear()
+        else:
+            self._dec_graphs.move_to_end(key)
+        direction = (src.data_ptr(), dst.data_ptr())
+        entry = rec.get(direction)
+        if entry is None:
+            def fn():
+                out = self._decode_fused_body(src, dst, tok32, par, cross_cache, cross_batch, kmask, pos_dev=pos_dev)
+                pos_dev.add_(1)
+                return out
+            entry = rec[direction] = self._capture(fn)     # (records only: the replay below runs the step)
+            self.dec_graph_captures += 1
+        entry[0].replay()
+        self.dec_graph_replays += 1
+        return entry[1]
 
     @torch.no_grad()
     @_with_attention_split

@@ -124,6 +124,7 @@ _beam_topk = _sig("mrblip_beam_topk", vp, ll, vp, vp, ll, i32, i32, i32, i32, i3
 _beam_advance = _sig("mrblip_beam_advance", vp, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp)
 _beam_finalize = _sig("mrblip_beam_finalize", vp, ll, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp)
 _kv_gather_rows = _sig("mrblip_kv_gather_rows", vp, vp, vp, i32, i32, i32, i32, i32, vp)
+_decode_self_attn = _sig("mrblip_decode_self_attention", vp, vp, vp, ll, vp, ll, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp)
 _crop_resize_u8 = _sig("mrblip_crop_resize_u8", vp, i32, i32, i32, C.POINTER(C.c_int), i32, i32, vp, i32, vp)
 
 EXPORTS = [
@@ -138,7 +139,7 @@ EXPORTS = [
     "mrblip_qformer_layer_fwd", "mrblip_layernorm_bwd_cast",
     "mrblip_gemm_f16", "mrblip_layernorm_fwd_f16", "mrblip_attention_fwd_rowv_f16", "mrblip_patchify_f16", "mrblip_patchify_u8_f16",
     "mrblip_beam_topk", "mrblip_beam_advance", "mrblip_beam_finalize", "mrblip_kv_gather_rows",
-    "mrblip_crop_resize_u8",
+    "mrblip_crop_resize_u8", "mrblip_decode_self_attention",
 ]
 
 
@@ -901,3 +902,34 @@ def kv_gather_rows(src, dst, parents, t: int):
     R, Lmax, inner = src.shape[-3:]
     assert parents.numel() == R
     _chk(_kv_gather_rows(_p(src), _p(dst), _p(parents), src.numel() // (R * Lmax * inner), R, Lmax, inner, int(t), _stream()))
+
+
+# ---- fused cached self-attention of generate's decode step (csrc/decode.hip)
+def decode_self_attention(kv_src, kv_dst, qkv, out, lut, layer: int, H: int, *, pos: Optional[int] = None, pos_dev=None, parents=None,
+                          scale: float = 1.0):
+    """One decoder layer's self-attention of ONE new position against the row-major cache [2, layers, R, Lmax, H * D] (bf16): re-orders
+    the rows by ``parents`` (int32 [R] on the device) from kv_src into kv_dst (the other buffer; without parents kv_dst is kv_src), appends
+    K / V of the new position from qkv [R, >= 3 * H * D] and writes the attention output to out [R, >= H * D].  lut: fp32 [H, 257]
+    relative-position bias.  Position: ``pos`` (host int) or ``pos_dev`` (int32 device word, never written)."""
+    _req(kv_src, torch.bfloat16, "decode_self_attention.kv_src"); _req(kv_dst, torch.bfloat16, "decode_self_attention.kv_dst")
+    _req(qkv, torch.bfloat16, "decode_self_attention.qkv"); _req(out, torch.bfloat16, "decode_self_attention.out")
+    _req(lut, torch.float32, "decode_self_attention.lut")
+    if kv_src.dim() != 5 or kv_src.shape[0] != 2 or not kv_src.is_contiguous() or not kv_dst.is_contiguous() or kv_dst.shape != kv_src.shape:
+        raise MrblipError(f"decode_self_attention: caches must be contiguous [2, layers, R, Lmax, H * D], got {tuple(kv_src.shape)} / {tuple(kv_dst.shape)}")
+    _, layers, R, Lmax, inner = kv_src.shape
+    if inner % int(H) != 0 or qkv.dim() != 2 or out.dim() != 2 or qkv.shape[0] != R or out.shape[0] != R or qkv.shape[1] < 3 * inner or out.shape[1] < inner:
+        raise MrblipError(f"decode_self_attention: H = {H}, inner = {inner}, qkv {tuple(qkv.shape)}, out {tuple(out.shape)} do not fit R = {R}")
+    if not lut.is_contiguous() or lut.numel() != int(H) * 257:
+        raise MrblipError(f"decode_self_attention: lut must be contiguous fp32 [H, 257], got {tuple(lut.shape)}")
+    if (pos is None) == (pos_dev is None):
+        raise MrblipError("decode_self_attention: give exactly one of pos (host int) and pos_dev (int32 device word)")
+    if pos_dev is not None:
+        _req(pos_dev, torch.int32, "decode_self_attention.pos_dev")
+        if pos_dev.numel() != 1:
+            raise MrblipError(f"decode_self_attention: pos_dev is one int32 word on the device, got {tuple(pos_dev.shape)}")
+    if parents is not None:
+        _req(parents, torch.int32, "decode_self_attention.parents")
+        if parents.numel() != R:
+            raise MrblipError(f"decode_self_attention: parents has {parents.numel()} entries, R = {R}")
+    _chk(_decode_self_attn(_p(kv_src), _p(kv_dst), _p(qkv), _ld(qkv), _p(out), _ld(out), _p(lut), _p(parents), _p(pos_dev),
+                           0 if pos is None else int(pos), layers, int(layer), R, Lmax, int(H), inner // int(H), float(scale), _stream()))

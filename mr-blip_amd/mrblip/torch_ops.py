@@ -18,6 +18,10 @@ the standard PyTorch extension point:
   mrblip::crop_resize_u8(src, boxes, out_size, frames_per_clip) -> dst   uint8 [.., 3, H, W] -> [.., 3, out, out]: one crop box per clip
                                                  (CPU int [n_clips, 4] of i, j, h, w) + bicubic resize; input augmentation, no autograd
 
+  mrblip::decode_self_attention(kv_src, kv_dst, qkv, out, lut, layer, heads, pos, pos_dev?, parents?, scale)   one decoder layer's
+                                                 single-query self-attention against the row-major K / V cache of an incremental decode:
+                                                 re-orders by parents, appends the new position, writes kv_dst and out in place; no autograd
+
 Every operator has a fake (meta) implementation, so FakeTensor tracing / torch.compile graph capture see shapes and dtypes without
 running a kernel.  CUDA (= HIP) tensors only: there is no CPU fallback, by design.
 """
@@ -294,5 +298,21 @@ def _(src, boxes, out_size, frames_per_clip=0):
     return src.new_empty(tuple(src.shape[:-2]) + (out_size, out_size))
 
 
+# ------------------------------------------------------------------------------------------------ incremental decode
+@custom_op("mrblip::decode_self_attention", mutates_args=("kv_dst", "out"), device_types="cuda")
+def decode_self_attention(kv_src: torch.Tensor, kv_dst: torch.Tensor, qkv: torch.Tensor, out: torch.Tensor, lut: torch.Tensor, layer: int,
+                          heads: int, pos: int = 0, pos_dev: Optional[torch.Tensor] = None, parents: Optional[torch.Tensor] = None,
+                          scale: float = 1.0) -> None:
+    """ops.decode_self_attention: caches bf16 [2, layers, R, Lmax, heads * D]; with ``parents`` (int32 [R]) kv_dst is the other cache buffer,
+    without it kv_dst must be kv_src's storage.  ``pos_dev`` (int32 [1]) replaces the host position ``pos``.  No gradient: inference only."""
+    ops.decode_self_attention(kv_src, kv_dst, qkv, out, lut, layer, heads, pos=None if pos_dev is not None else pos, pos_dev=pos_dev,
+                              parents=parents, scale=scale)
+
+
+@decode_self_attention.register_fake
+def _(kv_src, kv_dst, qkv, out, lut, layer, heads, pos=0, pos_dev=None, parents=None, scale=1.0):
+    return None
+
+
 OPS = ("gemm_", "linear", "linear_backward", "layer_norm", "layer_norm_backward", "rms_norm", "rms_norm_backward", "attention_forward",
-       "attention_backward", "cross_entropy_forward", "adamw_", "crop_resize_u8")
+       "attention_backward", "cross_entropy_forward", "adamw_", "crop_resize_u8", "decode_self_attention")
