@@ -203,6 +203,40 @@ int mrblip_gemm_set_thin(const void* acat, long long lda, int R, int K, uint32_t
 int mrblip_adamw_guarded(float* p, const float* g, float* m, float* v, long long n, const float* hyper, float beta1, float beta2, float eps,
                          float weight_decay, const uint32_t* guard, mrblip_stream_t stream);
 int mrblip_gemm_debug_stall_thin(int on);
+/* The gradient guard (csrc/optim.hip): global gradient norm, non-finite check, clipping by global norm and the optimizer clock, decided on
+ * the device in two launches in front of mrblip_adamw_guarded.  It is the counterpart of what GradScaler does besides scaling — check the
+ * gradients for inf / nan and SKIP the optimizer step (runner_base.py:127-132, moment_retrieval.py:221-233) — plus
+ * torch.nn.utils.clip_grad_norm_.  The library keeps no state of its own: workspace, state block and hyper blocks are the caller's.
+ *
+ * mrblip_grad_sumsq (usable alone) cuts the flat fp32 gradient g[0, n) into chunks of 16384 elements — chunk c is ALWAYS elements
+ *   [16384 c, min(16384 (c + 1), n)), whatever the grid — and writes one 16-byte record per chunk to ws:
+ *     { double sumsq;  uint32 nonfinite;  uint32 reserved; }      record c at byte offset 16 c
+ *   sumsq = sum of (double)g[i] * (double)g[i] over the chunk's finite values, nonfinite = its inf / nan values.  Every addition is fp64 in
+ *   an order fixed by the element index (and g's offset inside its 16-byte line): the records are the same bits for every grid, CU count
+ *   and run.  g may start at any 4-byte-aligned address; nothing outside [g, g + n) is read.  ws: 16-byte aligned, at least
+ *   mrblip_grad_stats_workspace_bytes(n) bytes (16 per chunk, at least 16).  n == 0 is legal and launches nothing.
+ * mrblip_optim_prepare adds the records of ws in chunk order (fp64), then with hyper_in = {lr, grad_scale} (2 floats, device):
+ *     norm = fp32(|grad_scale| * sqrt(S))                                  (pre-clip; an fp32 overflow counts as non-finite)
+ *     skip = nonfinite > 0 || !isfinite(norm) || (guard_in != NULL && *guard_in != 0)
+ *     clip = max_norm <= 0 ? 1 : min(1, max_norm / (norm + 1e-6))         (clip_grad_norm_'s formula)
+ *   applied:  state.applied += 1, t = state.applied, hyper_out = {lr, 1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t), grad_scale * clip} — the
+ *             block mrblip_adamw reads; both bias terms are computed in double on the device and rounded to fp32
+ *   skipped:  state.skipped += 1, state.applied unchanged, hyper_out unspecified
+ *   state: 8 uint32 words of device memory, read AND written (zero them before the first step, or preset applied / skipped from a checkpoint):
+ *     word 0  uint32 skip                0 = apply; hand &state[0] to mrblip_adamw_guarded as its guard
+ *     word 1  uint32 applied             optimizer steps applied so far: the optimizer clock
+ *     word 2  uint32 skipped             optimizer steps skipped so far
+ *     word 3  uint32 nonfinite           inf / nan values of THIS step's gradient, saturating
+ *     word 4  float  norm                this step's pre-clip norm, +inf when nonfinite != 0
+ *     word 5  float  clip                this step's clip factor (1 when skipped)
+ *     word 6  uint32 consecutive_skips   skipped steps since the last applied one
+ *     word 7  reserved (written as 0)
+ * The step is then two mrblip_adamw_guarded calls (decay / no-decay segment) with hyper = hyper_out and guard = &state[0].
+ * beta1, beta2 in [0, 1) (doubles: the bias terms then agree with a host that evaluates the same formulas in double); max_norm not NaN. */
+long long mrblip_grad_stats_workspace_bytes(long long n);
+int mrblip_grad_sumsq(const float* g, long long n, void* ws, long long ws_bytes, mrblip_stream_t stream);
+int mrblip_optim_prepare(const void* ws, long long n, const float* hyper_in, double beta1, double beta2, float max_norm, const uint32_t* guard_in,
+                         void* state, float* hyper_out, mrblip_stream_t stream);
 int mrblip_prefetch(const void* ptr, long long bytes, int n_blocks, mrblip_stream_t stream);
 /* LoRA r=8 (peft 0.13.0 Linear; blip2_mr.py:182-200,236).  The rank-8 products themselves run on mrblip_gemm_bf16
  * (u = drop(x) Acat^T, g = dy Bblk^T, dBt += u^T dy, dA += g^T drop(x) on transposed copies); these are the side pieces:

@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = ["errors.hip", "gemm.hip", "norm.hip", "attention.hip", "elementwise.hip", "lora.hip", "decproj.hip", "qformer.hip", "search.hip", "augment.hip", "decode.hip"]
+SRCS = ["errors.hip", "gemm.hip", "norm.hip", "attention.hip", "elementwise.hip", "lora.hip", "decproj.hip", "qformer.hip", "search.hip", "augment.hip", "decode.hip", "optim.hip"]
 HDRS = ["common.h", "lora_thin.h", os.path.join("..", "..", "include", "mrblip_hip.h")]   # (the public header: gemm.hip and qformer.hip include it)
 LIB = os.path.join(HERE, "libmrblip_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -13,6 +13,7 @@ from torch.utils.data import DataLoader, DistributedSampler
 from lavis.common.dist_utils import get_rank, get_world_size, is_dist_avail_and_initialized, is_main_process, main_process
 from lavis.common.registry import registry
 from mrblip import ops
+from mrblip.grad_guard import GradGuard, check_max_grad_norm
 
 
 class FlatAdamW:
@@ -20,13 +21,19 @@ class FlatAdamW:
     executed by the fused HIP kernel over the model's flat parameter / gradient buffers (decay segment | no-decay segment).
     ``grad_scale`` (1/world after a SUM all-reduce, x the model's own loss scale) is applied inside the kernel."""
 
-    def __init__(self, model, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, model, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_guard=False, max_grad_norm=None, max_consecutive_skips=8):
+        max_grad_norm = check_max_grad_norm(max_grad_norm)      # a finite number above 0 or None: ValueError before anything is allocated
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
         flat = getattr(model, "train_engine", model.engine).flat
         self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
         self.t = 0
         self.grad_scale = 1.0
         self.hyper = torch.zeros(4, device=flat.device)
+        # the gradient guard (mrblip/grad_guard.py, DESIGN.md §15), off by default: global norm + non-finite check + optional clipping
+        # on the device; a step with an inf / nan gradient is skipped and not counted.  max_grad_norm implies the guard.
+        self.grad_guard = bool(grad_guard) or max_grad_norm is not None
+        self.max_grad_norm = max_grad_norm
+        self.guard = GradGuard(flat.device, flat.numel(), max_grad_norm, max_consecutive_skips) if self.grad_guard else None
 
     def set_lr(self, lr):
         self.lr = lr
@@ -37,6 +44,8 @@ class FlatAdamW:
     @torch.no_grad()
     def step(self):
         eng = getattr(self.model, "train_engine", self.model.engine)
+        if self.guard is not None:
+            return self._guarded_step(eng)
         # (the verdict itself is only consumed at a step's ENTRY or at a blocking check point — never between a step and its own AdamW, which
         # must stay guarded by the error word: mrblip/engine.py check_thin_role)
         self.t = max(0, self.t - eng.consume_thin_skipped())    # steps the guarded kernel dropped on the device do not count (bias correction)
@@ -53,16 +62,52 @@ class FlatAdamW:
         ops.adamw(eng.flat[nd:], g[nd:], self.m[nd:], self.v[nd:], self.hyper, b1, b2, self.eps, 0.0, guard=guard)
         eng.refresh_trainable()
 
+    def _guarded_step(self, eng):
+        """grad_sumsq over the whole flat gradient, optim_prepare (which folds the thin role's error word into its verdict, counts the step
+        on the device and writes self.hyper), then the two guarded AdamW launches on the verdict.  The DEVICE counter is the optimizer
+        clock here: self.t takes no part in the bias correction, so nothing has to be rewound when a step was dropped on the device."""
+        self.guard.poll()                      # raises when an arrived state shows max_consecutive_skips skipped steps in a row
+        eng.consume_thin_skipped()             # (the engine's book-keeping stays as it is; the value is not needed: skipped steps never ticked the clock)
+        eng.note_optimizer_step()
+        b1, b2 = self.betas
+        g, nd = self.model.grad_buffer(), eng.n_decay
+        self.guard.prepare(g, self.lr, self.grad_scale * self.model.grad_scale(), (b1, b2), self.hyper,
+                           guard_in=eng.thin_guard() if eng.gemm_thin_enabled else None)
+        skip = self.guard.skip_word()
+        ops.adamw(eng.flat[:nd], g[:nd], self.m[:nd], self.v[:nd], self.hyper, b1, b2, self.eps, self.wd, guard=skip)
+        ops.adamw(eng.flat[nd:], g[nd:], self.m[nd:], self.v[nd:], self.hyper, b1, b2, self.eps, 0.0, guard=skip)
+        eng.refresh_trainable()
+
+    def stats(self, block=False):
+        """the newest step whose state has arrived on the host: {grad_norm (pre-clip, +inf for a non-finite gradient), clip, nonfinite,
+        skipped_step, applied_steps, skipped_steps}, or None (guard off / nothing arrived yet).  Waits only with block=True."""
+        return None if self.guard is None else self.guard.stats(block)
+
     def state_dict(self):
+        if self.guard is not None:             # the optimizer clock lives on the device: one blocking read, at a checkpoint only
+            st = self.guard.read()
+            self.t = st["applied_steps"]
+            return {"t": self.t, "skipped": st["skipped_steps"], "m": self.m, "v": self.v, "lr": self.lr}
         return {"t": self.t, "m": self.m, "v": self.v, "lr": self.lr}
 
     def load_state_dict(self, sd):
         self.t, self.lr = sd["t"], sd["lr"]
+        if self.guard is not None:             # (a checkpoint written without the guard has no "skipped": applied = t)
+            self.guard.set_clock(int(sd["t"]), int(sd.get("skipped", 0)))
         m, v = sd["m"], sd["v"]
         if isinstance(m, (list, tuple)):  # round-1 checkpoints kept the two segments apart
             m, v = torch.cat([x.reshape(-1) for x in m]), torch.cat([x.reshape(-1) for x in v])
         self.m.copy_(m)
         self.v.copy_(v)
+
+
+def grad_guard_options(run) -> dict:
+    """run.grad_guard (default False) and run.max_grad_norm (default None: no clipping; a finite number above 0, which implies the guard)
+    as FlatAdamW's keyword arguments"""
+    mgn = run.get("max_grad_norm", None)
+    if isinstance(mgn, str) and mgn.strip().lower() in ("", "none", "null"):
+        mgn = None
+    return {"grad_guard": bool(run.get("grad_guard", False)), "max_grad_norm": check_max_grad_norm(mgn)}
 
 
 @registry.register_runner("runner_base")
@@ -76,7 +121,7 @@ class RunnerBase:
         if registry.get_path("result_dir") is None:
             registry.register_path("result_dir", os.path.join(self.output_dir, "result"))
             registry.register_path("output_dir", self.output_dir)
-        self.optimizer = FlatAdamW(model, lr=float(run.init_lr), weight_decay=float(run.get("weight_decay", 0.05)))
+        self.optimizer = FlatAdamW(model, lr=float(run.init_lr), weight_decay=float(run.get("weight_decay", 0.05)), **grad_guard_options(run))
         sched_cls = registry.get_lr_scheduler_class(run.lr_sched)
         self.lr_scheduler = sched_cls(optimizer=self.optimizer, max_epoch=run.max_epoch, min_lr=float(run.min_lr), init_lr=float(run.init_lr),
                                       decay_rate=run.get("lr_decay_rate", None), warmup_start_lr=float(run.get("warmup_lr", -1)),

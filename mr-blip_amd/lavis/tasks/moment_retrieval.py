@@ -3,6 +3,7 @@
 the gradient all-reduce happens ONCE per optimizer step (accumulation boundary), not per micro-step."""
 import json
 import logging
+import math
 
 import numpy as np
 import torch
@@ -65,6 +66,20 @@ class MomentRetrievalTask(BaseTask):
         metric_logger = MetricLogger(delimiter="  ")
         iters_per_epoch = len(data_loader)
         model.train()
+        guarded = bool(getattr(optimizer, "grad_guard", False)) and hasattr(optimizer, "stats")
+        logged_steps = [0]   # gradient guard: optimizer steps whose norm has been logged (a state arrives one step late, like the loss)
+
+        def log_guard(log=True):
+            st = optimizer.stats(block=False)   # never waits: whatever state has arrived (None before the first one)
+            if st is not None and st["applied_steps"] + st["skipped_steps"] != logged_steps[0]:
+                logged_steps[0] = st["applied_steps"] + st["skipped_steps"]
+                if log:
+                    if math.isfinite(st["grad_norm"]):   # (a skipped step's norm is +inf: it shows in skipped_steps, not in the average)
+                        metric_logger.update(grad_norm=st["grad_norm"])
+                    metric_logger.update(skipped_steps=st["skipped_steps"])
+
+        if guarded:
+            log_guard(log=False)   # (what an earlier epoch already logged)
         pending_loss = None  # the loss is read ONE step late: loss.item() right after the step (the reference's loop, :234) drains the
         #                      stream, and with ~2900 launches per step the host would then re-fill the queue while the GPU idles
         for i, (samples, nxt) in enumerate(_with_next(metric_logger.log_every(data_loader, log_freq, f"Train: data epoch: [{epoch}]"))):
@@ -83,12 +98,16 @@ class MomentRetrievalTask(BaseTask):
                     reduce_grads()
                 optimizer.step()
                 optimizer.zero_grad()
+                if guarded:
+                    log_guard()
             if pending_loss is not None:
                 metric_logger.update(loss=pending_loss.item())
             pending_loss = loss.detach()
             metric_logger.update(lr=optimizer.lr)
         if pending_loss is not None:
             metric_logger.update(loss=pending_loss.item())
+        if guarded:
+            log_guard()            # (the wait for the last loss has let the states of the earlier steps arrive)
         metric_logger.synchronize_between_processes()
         logging.info("Averaged stats: " + metric_logger.global_avg())
         return {k: "{:.3f}".format(m.global_avg) for k, m in metric_logger.meters.items()}

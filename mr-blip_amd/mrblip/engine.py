@@ -2901,11 +2901,34 @@ class MrBlipEngine:
                 "step's encoder activations and LoRA gradients may be wrong.  The guarded AdamW has skipped every optimizer step since; "
                 "set MRB_GEMM_THIN=0 (the thin product as a launch of its own) to run without the role, and report the configuration")
 
+    _grad_guard = None            # mrblip.grad_guard.GradGuard of optimizer_step(grad_guard=True), built on first use
+
+    def grad_guard(self, max_grad_norm=None):
+        """the engine's own guard block (device state + deferred host view); max_grad_norm may change from call to call"""
+        from .grad_guard import GradGuard, check_max_grad_norm
+        if self._grad_guard is None:
+            self._grad_guard = GradGuard(self.dev, self.grad.numel())
+        self._grad_guard.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        return self._grad_guard
+
     @torch.no_grad()
     def optimizer_step(self, lr: float, weight_decay: float = 0.05, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                       grad_scale: float = 1.0):
+                       grad_scale: float = 1.0, grad_guard: bool = False, max_grad_norm=None):
         """AdamW(beta=(0.9,0.999), wd on >=2-D non-bias/ln params) as in runner_base.py:102-132.  Guarded by the thin role's error word: see
-        check_thin_role."""
+        check_thin_role.  grad_guard / max_grad_norm (off by default; max_grad_norm implies the guard): the gradient guard of DESIGN.md §15
+        — a step whose gradient holds an inf / nan is skipped on the device, the gradient is clipped to max_grad_norm, and the device
+        counter of APPLIED steps is the optimizer clock (opt_step is then not used); self.grad_guard().stats() / .read() report."""
+        if grad_guard or max_grad_norm is not None:
+            guard = self.grad_guard(max_grad_norm)
+            guard.poll()
+            self.note_optimizer_step()
+            nd = self.n_decay
+            guard.prepare(self.grad, lr, grad_scale, (beta1, beta2), self.hyper, guard_in=self.thin_guard() if self.gemm_thin_enabled else None)
+            skip = guard.skip_word()
+            ops.adamw(self.flat[:nd], self.grad[:nd], self.adam_m[:nd], self.adam_v[:nd], self.hyper, beta1, beta2, eps, weight_decay, guard=skip)
+            ops.adamw(self.flat[nd:], self.grad[nd:], self.adam_m[nd:], self.adam_v[nd:], self.hyper, beta1, beta2, eps, 0.0, guard=skip)
+            self.refresh_trainable()
+            return
         self.opt_step += 1
         self.note_optimizer_step()
         t = self.opt_step

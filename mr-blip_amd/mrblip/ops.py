@@ -126,6 +126,10 @@ _beam_finalize = _sig("mrblip_beam_finalize", vp, ll, vp, vp, vp, vp, vp, vp, i3
 _kv_gather_rows = _sig("mrblip_kv_gather_rows", vp, vp, vp, i32, i32, i32, i32, i32, vp)
 _decode_self_attn = _sig("mrblip_decode_self_attention", vp, vp, vp, ll, vp, ll, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp)
 _crop_resize_u8 = _sig("mrblip_crop_resize_u8", vp, i32, i32, i32, C.POINTER(C.c_int), i32, i32, vp, i32, vp)
+_grad_sumsq = _sig("mrblip_grad_sumsq", vp, ll, vp, ll, vp)
+_optim_prepare = _sig("mrblip_optim_prepare", vp, ll, vp, C.c_double, C.c_double, f32, vp, vp, vp, vp)
+_lib.mrblip_grad_stats_workspace_bytes.argtypes = [ll]
+_lib.mrblip_grad_stats_workspace_bytes.restype = ll
 
 EXPORTS = [
     "mrblip_last_error", "mrblip_abi_version", "mrblip_gemm_bf16", "mrblip_layernorm_fwd", "mrblip_rmsnorm_fwd",
@@ -140,6 +144,7 @@ EXPORTS = [
     "mrblip_gemm_f16", "mrblip_layernorm_fwd_f16", "mrblip_attention_fwd_rowv_f16", "mrblip_patchify_f16", "mrblip_patchify_u8_f16",
     "mrblip_beam_topk", "mrblip_beam_advance", "mrblip_beam_finalize", "mrblip_kv_gather_rows",
     "mrblip_crop_resize_u8", "mrblip_decode_self_attention",
+    "mrblip_grad_stats_workspace_bytes", "mrblip_grad_sumsq", "mrblip_optim_prepare",
 ]
 
 
@@ -830,6 +835,52 @@ def adamw(p, g, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
         _chk(_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), beta1, beta2, eps, weight_decay, _stream()))
     else:
         _chk(_adamw_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), beta1, beta2, eps, weight_decay, _p(guard), _stream()))
+
+
+# ---- gradient guard (csrc/optim.hip; driven by mrblip.grad_guard.GradGuard): norm, non-finite check, clipping and the optimizer clock
+GRAD_CHUNK = 16384        # elements per workspace record
+OPTIM_STATE_WORDS = 8     # uint32 words of the state block (layout: include/mrblip_hip.h)
+
+
+def grad_stats_workspace_bytes(n: int) -> int:
+    b = int(_lib.mrblip_grad_stats_workspace_bytes(int(n)))
+    if b < 0:
+        raise MrblipError(f"grad_stats_workspace_bytes: n = {n} < 0")
+    return b
+
+
+def grad_sumsq(g, ws):
+    """ws (uint8, >= grad_stats_workspace_bytes(g.numel())) <- one {fp64 sum of squares, uint32 non-finite count} record per 16384-element
+    chunk of the flat fp32 gradient g (contiguous, any 4-byte-aligned start).  Bit-reproducible: fixed chunks, fixed fp64 order."""
+    _req(g, torch.float32, "grad_sumsq.g")
+    if g.dim() != 1:
+        raise MrblipError(f"grad_sumsq.g: expected a flat buffer, got {tuple(g.shape)}")
+    _chk(_grad_sumsq(_p(g), g.numel(), _p(ws), ws.numel() * ws.element_size(), _stream()))
+
+
+def optim_prepare(ws, n: int, hyper_in, state, hyper_out, beta1=0.9, beta2=0.999, max_norm=0.0, guard=None):
+    """The records of grad_sumsq(g[:n]) -> the step's decision.  hyper_in fp32 [2] = (lr, grad_scale); state int32 [8] (read and written:
+    skip, applied, skipped, nonfinite, norm, clip, consecutive_skips, reserved); hyper_out fp32 [4] = AdamW's hyper block with the bias
+    terms of step state.applied and grad_scale * clip; guard (optional int32 word): non-zero skips the step as a non-finite gradient does."""
+    _req(hyper_in, torch.float32, "optim_prepare.hyper_in")
+    _req(hyper_out, torch.float32, "optim_prepare.hyper_out")
+    _req(state, torch.int32, "optim_prepare.state")
+    if hyper_in.numel() < 2 or hyper_out.numel() < 4 or state.numel() < OPTIM_STATE_WORDS or ws.numel() * ws.element_size() < grad_stats_workspace_bytes(n):
+        raise MrblipError("optim_prepare: hyper_in [2], hyper_out [4], state [8] and a workspace of grad_stats_workspace_bytes(n) are needed")
+    _chk(_optim_prepare(_p(ws), int(n), _p(hyper_in), float(beta1), float(beta2), float(max_norm), _p(guard), _p(state), _p(hyper_out), _stream()))
+
+
+def grad_norm(g, grad_scale: float = 1.0):
+    """(norm fp32 [1], nonfinite int32 [1]) of the flat fp32 gradient g: |grad_scale| * sqrt(sum g^2) accumulated in fp64 and rounded once;
+    +inf when g holds an inf / nan (their count: nonfinite) or the norm overflows fp32.  Two launches, no host synchronisation."""
+    _req(g, torch.float32, "grad_norm.g")
+    g = g.reshape(-1)
+    ws = torch.empty(grad_stats_workspace_bytes(g.numel()), dtype=torch.uint8, device=g.device)
+    state = torch.zeros(OPTIM_STATE_WORDS, dtype=torch.int32, device=g.device)
+    hyper = torch.tensor([0.0, float(grad_scale), 0.0, 0.0, 0.0, 0.0], dtype=torch.float32).to(g.device)
+    grad_sumsq(g, ws)
+    optim_prepare(ws, g.numel(), hyper[:2], state, hyper[2:])
+    return state[4:5].view(torch.float32), state[3:4]
 
 
 def seed_bump(seed):

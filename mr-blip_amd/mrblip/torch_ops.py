@@ -14,6 +14,8 @@ the standard PyTorch extension point:
   mrblip::attention(q, k, v, scale, bias_lut?, kmask?, causal) -> o     bf16 [B,S,H,D], D <= 64 for the backward
   mrblip::cross_entropy(logits, labels) -> loss  fp32 [R,V], int32 [R] (-100 = ignore) -> mean over valid rows, fp32 [1]
   mrblip::adamw_(p, g, m, v, hyper, ...)         in-place fused AdamW over flat fp32 buffers
+  mrblip::grad_norm(g) -> (norm, nonfinite)      flat fp32 gradient -> (fp32 [1] global L2 norm, fp64-accumulated and bit-reproducible;
+                                                 int32 [1] count of inf / nan values, norm = +inf when non-zero); no host synchronisation
   mrblip::gemm_(a, w, out, bias?, residual?, act, tile_cfg)   the raw fused GEMM, writing ``out`` in place
   mrblip::crop_resize_u8(src, boxes, out_size, frames_per_clip) -> dst   uint8 [.., 3, H, W] -> [.., 3, out, out]: one crop box per clip
                                                  (CPU int [n_clips, 4] of i, j, h, w) + bicubic resize; input augmentation, no autograd
@@ -285,6 +287,18 @@ def _(p, g, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
     return None
 
 
+@custom_op("mrblip::grad_norm", mutates_args=(), device_types="cuda")
+def grad_norm(g: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ops.grad_norm: the global L2 norm of a flat fp32 gradient and its count of non-finite values (csrc/optim.hip).  No gradient."""
+    norm, bad = ops.grad_norm(_c(g))
+    return norm.clone(), bad.clone()
+
+
+@grad_norm.register_fake
+def _(g):
+    return g.new_empty(1, dtype=f32), g.new_empty(1, dtype=torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------ input augmentation
 @custom_op("mrblip::crop_resize_u8", mutates_args=(), device_types="cuda")
 def crop_resize_u8(src: torch.Tensor, boxes: torch.Tensor, out_size: int, frames_per_clip: int = 0) -> torch.Tensor:
@@ -315,4 +329,4 @@ def _(kv_src, kv_dst, qkv, out, lut, layer, heads, pos=0, pos_dev=None, parents=
 
 
 OPS = ("gemm_", "linear", "linear_backward", "layer_norm", "layer_norm_backward", "rms_norm", "rms_norm_backward", "attention_forward",
-       "attention_backward", "cross_entropy_forward", "adamw_", "crop_resize_u8", "decode_self_attention")
+       "attention_backward", "cross_entropy_forward", "adamw_", "crop_resize_u8", "decode_self_attention", "grad_norm")
