@@ -451,6 +451,37 @@ int mrblip_beam_finalize(const int* seq, long long lds, const float* beam_scores
  * [2, layers, R, Lmax, inner] with planes = 2 * layers), parents read on the device: HF's _reorder_cache(beam_idx) without the host
  * (search.py:94-97).  src != dst, because parents repeat.  inner % 8 == 0; an index outside 0..R-1 copies the row itself. */
 int mrblip_kv_gather_rows(const void* src, void* dst, const int* parents, int planes, int R, int Lmax, int inner, int t, mrblip_stream_t stream);
+/* Device-resident sampler of generate (csrc/search.hip): mrblip/search.py sample_search — HF's multinomial sampling (do_sample=True:
+ * repetition penalty, min-length EOS ban, temperature, top-k, top-p, one draw per row) and its greedy decoding on raw logits — with every
+ * piece of state in the caller's device memory (int32; the library keeps none).  R <= 256 rows, V <= 131072, 1 <= top_k <= 64,
+ * k = min(top_k, V): anything else is rejected before any launch.  No float atomics, fixed orders: two runs give the same bits.
+ *
+ * mrblip_sample_topk: for each row the k best WARPED RAW logits, best first, into cand_score / cand_index [R, 64] (row stride 64; slots
+ * k..63 are set to -inf / -1).  The warp, in fp32: x = x < 0 ? x * p : x / p for every token id among the row's first cur_len sequence
+ * tokens (only if p = repetition_penalty != 1), then x[eos_id] = -inf while cur_len < min_length.  Order: higher score first, equal scores
+ * by lower token id; when fewer than k entries are finite the remaining slots carry -inf, in index order.  The temperature is not applied
+ * (it preserves the order).  logits fp32 [R, V], ld = ldl; seqs int32 [R, >= cur_len], ld = lds.  Two launches: the k best of every
+ * 2048-entry chunk, then a merge per row.  ws: caller-owned scratch of mrblip_sample_topk_workspace_bytes(R, top_k, V) =
+ * 8 * R * ceil(V / 2048) * k bytes (-1 for a rejected shape), 16-byte aligned, no initial state needed. */
+long long mrblip_sample_topk_workspace_bytes(int R, int top_k, int V);
+int mrblip_sample_topk(const float* logits, long long ldl, const int* seqs, long long lds, int R, int V, int cur_len, int top_k, int min_length,
+                       int eos_id, float repetition_penalty, float* cand_score, int* cand_index, void* ws, long long ws_bytes,
+                       mrblip_stream_t stream);
+/* One decoding step of all R rows on the candidates of mrblip_sample_topk, one launch.  Per row, in fp64 (temperature and top_p are
+ * widened from fp32), every sum sequential in rank order:
+ *   w_i = (double)cand_score_i / temperature, p_i = exp(w_i - w_0), P_i = p_0 + ... + p_i, Z = P_{k-1};
+ *   top-p cut (HF's TopPLogitsWarper for a descending list): rank 0 is kept, rank i >= 1 iff Z - P_{i-1} > (1 - top_p) * Z; the kept set is
+ *   the prefix of n ranks that ends before the first rank that fails.  top_p >= 1 keeps every rank with p_i > 0;
+ *   draw: target = u * P_{n-1}, the token is the first rank i < n with P_i > target, rank n - 1 if there is none;
+ *   u = uniforms[t * R + r] (fp32 in [0, 1), t = cur_len - 1) or, with uniforms == NULL, (hash(r * 256 + t, seed, site) >> 8) * 2^-24 with
+ *   the library's counter hash (csrc/common.h mrb_hash, site MRB_SITE_SAMPLE); cur_len <= 256 in that form.
+ * greedy != 0: the token is rank 0 (no temperature, no cut, no draw).  Then sample_search's bookkeeping: a row with unfinished[r] == 0
+ * emits pad_id; the token goes to seq[r, cur_len] and tokens[r]; a row that emits eos_id gets unfinished[r] = 0 and length[r] = cur_len + 1
+ * (the position after its first EOS); done_count[0] = number of rows with unfinished == 0.  A candidate index outside 0..V-1 (a row of
+ * NaNs) becomes pad_id.  temperature > 0, top_p > 0, lds >= cur_len + 1, 0 <= pad_id < V. */
+int mrblip_sample_advance(const float* cand_score, const int* cand_index, int* seq, long long lds, int* tokens, int* unfinished, int* length,
+                          int* done_count, const float* uniforms, uint32_t seed, int R, int V, int top_k, int cur_len, int eos_id, int pad_id,
+                          float temperature, float top_p, int greedy, mrblip_stream_t stream);
 /* Single-query self-attention of one decoder layer against the row-major self-attention cache of an incremental decode (csrc/decode.hip):
  * kv_src / kv_dst bf16 [2 (k, v), layers, R, Lmax, inner], inner = H * D.  One launch, a workgroup per (row r, head h), with
  * p = parents ? parents[r] : r (an index outside 0..R-1 is treated as r):

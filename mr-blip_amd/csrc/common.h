@@ -112,6 +112,8 @@ __device__ __forceinline__ uint32_t mrb_hash(uint32_t idx, uint32_t seed, uint32
   h ^= h >> 13;
   return h;
 }
+// site of the device sampler's draws (search.hip: one hash per row and decoding step, idx = row * 256 + step, seed = the call's seed)
+#define MRB_SITE_SAMPLE 0x53414D50u
 // One 32-bit hash serves the element PAIR (idx & ~1, idx | 1): even index -> low 16 bits, odd index -> high 16 bits.
 // keep iff the 16-bit draw >= thresh16 = round(p * 65536)   (p = 0.1 -> 6554/65536 = 0.10001)
 // s_waitcnt vmcnt(0) as an INSTRUCTION the compiler's wait-count pass sees (gfx9 encoding: vmcnt 0, expcnt 7, lgkmcnt 15).  Placed between a

@@ -4,6 +4,9 @@
 //
 // ORDER of candidates everywhere: higher score first, equal scores by LOWER flat index (beam * V + token); pool entries: higher score
 // first, equal scores by lower pool slot.  (At step 0 the beams 1..K-1 carry -1e9 and all their candidates tie exactly.)
+//
+// Second half of the file: the device-resident sampler (mrblip/search.py sample_search — nucleus sampling and greedy decoding on warped raw
+// logits), which shares the per-chunk selection with the beam search.
 #include "common.h"
 #include "../../include/mrblip_hip.h"
 #include <limits.h>
@@ -46,6 +49,37 @@ __device__ __forceinline__ Key block_best(Key k, Key* slot) {
   for (int w = 1; w < 4; ++w)
     if (key_before(slot[w], b)) b = slot[w];
   return b;
+}
+
+// LDS bitmap of the chunk [base, base + BS_CHUNK): bit set for every token id among the row's first cur_len sequence tokens (the
+// repetition penalty's set; left empty when pen == 1).  256 lanes; the bitmap is complete when the call returns.
+__device__ __forceinline__ void chunk_mark_seen(uint32_t* seen, const int* __restrict__ seq_row, int cur_len, int base, float pen) {
+  const int tid = threadIdx.x;
+  if (tid < BS_CHUNK / 32) seen[tid] = 0u;
+  __syncthreads();
+  if (pen != 1.0f) {
+    for (int j = tid; j < cur_len; j += 256) {
+      const int t = seq_row[j] - base;
+      if (t >= 0 && t < BS_CHUNK) atomicOr(&seen[t >> 5], 1u << (t & 31));   // (integer OR: order free)
+    }
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ bool chunk_seen(const uint32_t* seen, int c) { return (seen[c >> 5] >> (c & 31)) & 1u; }
+// the n best of the workgroup's 256 x 8 keys, best first, to os / oi (key_none once the chunk is exhausted): n selections without marking
+__device__ __forceinline__ void chunk_select(const Key (&mine)[8], int n, Key (*slots)[4], float* __restrict__ os, int* __restrict__ oi) {
+  Key last = {INFINITY, -1};
+  for (int it = 0; it < n; ++it) {
+    Key b = key_none();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b = key_pick(b, mine[j], last);
+    b = block_best(b, slots[it & 1]);
+    if (threadIdx.x == 0) {
+      os[it] = b.s;
+      oi[it] = b.i;
+    }
+    last = b;
+  }
 }
 
 // ---- pass 1: per (row, vocabulary chunk) the maximum and the sum of exp(x - max)
@@ -91,15 +125,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
   const int base = sp * BS_CHUNK;
   __shared__ uint32_t seen[BS_CHUNK / 32];
   __shared__ Key slots[2][4];
-  if (tid < BS_CHUNK / 32) seen[tid] = 0u;
-  __syncthreads();
-  if (pen != 1.0f) {
-    for (int j = tid; j < cur_len; j += 256) {
-      const int t = seqs[(long long)row * lds_ + j] - base;
-      if (t >= 0 && t < BS_CHUNK) atomicOr(&seen[t >> 5], 1u << (t & 31));   // (integer OR: order free)
-    }
-  }
-  __syncthreads();
+  chunk_mark_seen(seen, seqs + (long long)row * lds_, cur_len, base, pen);
   // log-sum-exp of the row from the chunk partials, in chunk order
   float M = -INFINITY;
   for (int s = 0; s < NS; ++s) M = fmaxf(M, pm[row * NS + s]);
@@ -119,26 +145,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
     mine[j] = key_none();
     if (v < V) {
       float lp = x[v] - lse;
-      if ((seen[c >> 5] >> (c & 31)) & 1u) lp = lp < 0.f ? lp * pen : lp / pen;
+      if (chunk_seen(seen, c)) lp = lp < 0.f ? lp * pen : lp / pen;
       if (eos_masked && v == eos_id) lp = -INFINITY;
       mine[j].s = lp + bs;
       mine[j].i = beam * V + v;
     }
   }
-  Key last = {INFINITY, -1};
-  float* os = part_s + ((long long)row * NS + sp) * 2 * K;
-  int* oi = part_i + ((long long)row * NS + sp) * 2 * K;
-  for (int it = 0; it < 2 * K; ++it) {
-    Key b = key_none();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b = key_pick(b, mine[j], last);
-    b = block_best(b, slots[it & 1]);
-    if (tid == 0) {
-      os[it] = b.s;
-      oi[it] = b.i;
-    }
-    last = b;
-  }
+  chunk_select(mine, 2 * K, slots, part_s + ((long long)row * NS + sp) * 2 * K, part_i + ((long long)row * NS + sp) * 2 * K);
 }
 
 // ---- pass 3: per clip, merge the K * NS sorted lists into the clip's 2K best (a lane owns up to four lists and offers their heads)
@@ -356,6 +369,136 @@ __global__ __launch_bounds__(256) void kv_gather_rows_kernel(const uint4* __rest
   for (long long i = (long long)blockIdx.z * 256 + threadIdx.x; i < n16; i += 256ll * gridDim.z) d[i] = s[i];
 }
 
+// ================================================================================================ device-resident sampler
+// mrblip/search.py sample_search on device state.  Candidates are WARPED RAW LOGITS (no log-softmax pass: a softmax is only ever needed
+// over the k <= 64 survivors); order: higher score first, equal scores by lower token id.
+#define SS_MAX_K 64
+#define SS_MAX_ROWS 256
+
+// ---- pass 1: per (row, chunk) the k best warped logits of the chunk, best first
+__global__ __launch_bounds__(256) void sample_select_kernel(const float* __restrict__ logits, long long ldl, const int* __restrict__ seqs,
+                                                             long long lds_, int NS, int k, int V, int cur_len, int eos_masked, int eos_id, float pen,
+                                                             float* __restrict__ part_s, int* __restrict__ part_i) {
+  const int row = blockIdx.y, sp = blockIdx.x, tid = threadIdx.x;
+  const int base = sp * BS_CHUNK;
+  __shared__ uint32_t seen[BS_CHUNK / 32];
+  __shared__ Key slots[2][4];
+  chunk_mark_seen(seen, seqs + (long long)row * lds_, cur_len, base, pen);
+  const float* x = logits + (long long)row * ldl;
+  Key mine[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = j * 256 + tid, v = base + c;
+    mine[j] = key_none();
+    if (v < V) {
+      float s = x[v];
+      if (chunk_seen(seen, c)) s = s < 0.f ? s * pen : s / pen;
+      if (eos_masked && v == eos_id) s = -INFINITY;
+      mine[j].s = s;
+      mine[j].i = v;
+    }
+  }
+  chunk_select(mine, k, slots, part_s + ((long long)row * NS + sp) * k, part_i + ((long long)row * NS + sp) * k);
+}
+
+// ---- pass 2: per row, merge the NS <= 64 sorted lists (lane l offers the head of list l) into cand[row, 0..k); slots k..63: (-inf, -1)
+__global__ __launch_bounds__(64) void sample_merge_kernel(const float* __restrict__ part_s, const int* __restrict__ part_i, int NS, int k,
+                                                          float* __restrict__ cand_s, int* __restrict__ cand_i) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* ls = part_s + ((long long)row * NS + tid) * k;
+  const int* li = part_i + ((long long)row * NS + tid) * k;
+  int ptr = 0;
+  for (int it = 0; it < k; ++it) {
+    Key head = key_none();
+    if (tid < NS && ptr < k) {
+      head.s = ls[ptr];
+      head.i = li[ptr];
+    }
+    const Key best = wave_best(head);
+    if (tid == 0) {
+      cand_s[row * SS_MAX_K + it] = best.s;
+      cand_i[row * SS_MAX_K + it] = best.i;
+    }
+    if (best.i != INT_MAX && head.i == best.i) ptr++;   // (token ids are unique within a row)
+  }
+  if (tid >= k) {
+    cand_s[row * SS_MAX_K + tid] = -INFINITY;
+    cand_i[row * SS_MAX_K + tid] = -1;
+  }
+}
+
+struct SampleArgs {
+  const float* cand_s;
+  const int* cand_i;
+  int* seq;
+  long long lds;
+  int *tokens, *unfinished, *length, *done_count;
+  const float* uniforms;
+  uint32_t seed;
+  int R, V, k, cur_len, eos_id, pad_id, greedy;
+  float temperature, top_p;
+};
+
+// rank drawn for one row: softmax over the k candidates at the temperature, HF's top-p cut restated for a descending list, one draw.
+// fp64 over at most 64 values, every sum sequential in rank order, no contraction: the decisions can be reproduced bit for bit on a host.
+__device__ int sample_rank(const float* __restrict__ cs, int k, double T, double top_p, double u) {
+#pragma clang fp contract(off)
+  const double w0 = (double)cs[0] / T;
+  double Z = 0.0;
+  for (int i = 0; i < k; ++i) Z += exp((double)cs[i] / T - w0);
+  // the kept set is a prefix of n ranks; P = P_{n-1}
+  const double thr = (1.0 - top_p) * Z;
+  double P = exp(w0 - w0);
+  int n = 1;
+  for (int i = 1; i < k; ++i) {
+    const double p = exp((double)cs[i] / T - w0);
+    const bool keep = top_p >= 1.0 ? p > 0.0 : Z - P > thr;   // (P is P_{i-1} here)
+    if (!keep) break;
+    P += p;
+    n = i + 1;
+  }
+  const double target = u * P;
+  double acc = 0.0;
+  for (int i = 0; i < n; ++i) {
+    acc += exp((double)cs[i] / T - w0);
+    if (acc > target) return i;
+  }
+  return n - 1;
+}
+
+// ---- search.py sample_search lines 70-82 for every row: one workgroup, lane r owns row r
+__global__ __launch_bounds__(SS_MAX_ROWS) void sample_advance_kernel(const SampleArgs a) {
+  const int r = threadIdx.x;
+  int finished = 0;
+  if (r < a.R) {
+    const float* cs = a.cand_s + r * SS_MAX_K;
+    int rank = 0;
+    if (!a.greedy && a.k > 1) {
+      const int t = a.cur_len - 1;
+      const double u = a.uniforms ? (double)a.uniforms[(long long)t * a.R + r]
+                                  : (double)(mrb_hash((uint32_t)(r * 256 + t), a.seed, MRB_SITE_SAMPLE) >> 8) * (1.0 / 16777216.0);
+      rank = sample_rank(cs, a.k, (double)a.temperature, (double)a.top_p, u);
+    }
+    int tok = a.cand_i[r * SS_MAX_K + rank];
+    if (tok < 0 || tok >= a.V) tok = a.pad_id;   // (a row of NaNs ranks nothing: never hand the decoder an index outside its table)
+    int unf = a.unfinished[r];
+    if (!unf) tok = a.pad_id;
+    a.seq[r * a.lds + a.cur_len] = tok;
+    a.tokens[r] = tok;
+    if (unf && tok == a.eos_id) {
+      unf = 0;
+      a.unfinished[r] = 0;
+      a.length[r] = a.cur_len + 1;
+    }
+    finished = !unf;
+  }
+  __shared__ int part[SS_MAX_ROWS / 64];
+  const int n = __popcll(__ballot(finished));
+  if ((r & 63) == 0) part[r >> 6] = n;
+  __syncthreads();
+  if (r == 0) a.done_count[0] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
 }  // namespace
 
 extern "C" int mrblip_beam_topk(const float* logits, long long ldl, const float* beam_scores, const int* seqs, long long lds_, int R, int K, int V,
@@ -419,4 +562,50 @@ extern "C" int mrblip_kv_gather_rows(const void* src, void* dst, const int* pare
   const int nz = (int)((n16 + 2047) / 2048 > 8 ? 8 : (n16 + 2047) / 2048);
   hipLaunchKernelGGL(kv_gather_rows_kernel, dim3(R, planes, nz), dim3(256), 0, stream, (const uint4*)src, (uint4*)dst, parents, R, row16, n16);
   return mrblip_check_launch("mrblip_kv_gather_rows");
+}
+
+static int sample_shape_ok(const char* who, int R, int V, int top_k) {
+  MRB_REQUIRE(top_k >= 1 && top_k <= SS_MAX_K, "%s: top_k = %d, 1..%d supported", who, top_k, SS_MAX_K);
+  MRB_REQUIRE(R >= 1 && R <= SS_MAX_ROWS, "%s: R = %d rows, 1..%d supported", who, R, SS_MAX_ROWS);
+  MRB_REQUIRE(V >= 1 && V <= BS_MAX_SPLIT * BS_CHUNK, "%s: V = %d, 1..%d supported", who, V, BS_MAX_SPLIT * BS_CHUNK);
+  return MRBLIP_OK;
+}
+
+extern "C" long long mrblip_sample_topk_workspace_bytes(int R, int top_k, int V) {
+  if (sample_shape_ok("mrblip_sample_topk_workspace_bytes", R, V, top_k) != MRBLIP_OK) return -1;
+  const int NS = (V + BS_CHUNK - 1) / BS_CHUNK, k = top_k < V ? top_k : V;
+  return 8ll * R * NS * k;
+}
+
+extern "C" int mrblip_sample_topk(const float* logits, long long ldl, const int* seqs, long long lds_, int R, int V, int cur_len, int top_k,
+                                  int min_length, int eos_id, float repetition_penalty, float* cand_score, int* cand_index, void* ws,
+                                  long long ws_bytes, hipStream_t stream) {
+  if (sample_shape_ok("mrblip_sample_topk", R, V, top_k) != MRBLIP_OK) return MRBLIP_EINVAL;
+  MRB_REQUIRE(cur_len >= 1 && lds_ >= cur_len && ldl >= V && repetition_penalty > 0.f, "mrblip_sample_topk: bad cur_len / leading dimension / penalty");
+  const int NS = (V + BS_CHUNK - 1) / BS_CHUNK, k = top_k < V ? top_k : V;
+  const long long need = 8ll * R * NS * k;
+  MRB_REQUIRE(logits && seqs && cand_score && cand_index && ws && ws_bytes >= need && ((uintptr_t)ws % 16) == 0,
+              "mrblip_sample_topk: null buffer or workspace below %lld bytes (8 * R * ceil(V / 2048) * min(top_k, V))", need);
+  float* part_s = (float*)ws;
+  int* part_i = (int*)(part_s + (long long)R * NS * k);
+  hipLaunchKernelGGL(sample_select_kernel, dim3(NS, R), dim3(256), 0, stream, logits, ldl, seqs, lds_, NS, k, V, cur_len, cur_len < min_length ? 1 : 0,
+                     eos_id, repetition_penalty, part_s, part_i);
+  hipLaunchKernelGGL(sample_merge_kernel, dim3(R), dim3(64), 0, stream, part_s, part_i, NS, k, cand_score, cand_index);
+  return mrblip_check_launch("mrblip_sample_topk");
+}
+
+extern "C" int mrblip_sample_advance(const float* cand_score, const int* cand_index, int* seq, long long lds_, int* tokens, int* unfinished,
+                                     int* length, int* done_count, const float* uniforms, uint32_t seed, int R, int V, int top_k, int cur_len,
+                                     int eos_id, int pad_id, float temperature, float top_p, int greedy, hipStream_t stream) {
+  if (sample_shape_ok("mrblip_sample_advance", R, V, top_k) != MRBLIP_OK) return MRBLIP_EINVAL;
+  MRB_REQUIRE(temperature > 0.f && top_p > 0.f, "mrblip_sample_advance: temperature = %g, top_p = %g (both have to be positive)", (double)temperature,
+              (double)top_p);
+  MRB_REQUIRE(cur_len >= 1 && lds_ >= cur_len + 1, "mrblip_sample_advance: sequence rows of %lld hold no position %d", lds_, cur_len);
+  MRB_REQUIRE(uniforms || cur_len <= 256, "mrblip_sample_advance: the built-in draws cover 256 steps, step %d needs caller-provided uniforms", cur_len - 1);
+  MRB_REQUIRE(pad_id >= 0 && pad_id < V, "mrblip_sample_advance: pad_id = %d outside the vocabulary of %d", pad_id, V);
+  MRB_REQUIRE(cand_score && cand_index && seq && tokens && unfinished && length && done_count, "mrblip_sample_advance: null buffer");
+  SampleArgs a = {cand_score, cand_index, seq, lds_, tokens, unfinished, length, done_count, uniforms, seed, R, V, top_k < V ? top_k : V, cur_len, eos_id,
+                  pad_id, greedy ? 1 : 0, temperature, top_p};
+  hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(SS_MAX_ROWS), 0, stream, a);
+  return mrblip_check_launch("mrblip_sample_advance");
 }

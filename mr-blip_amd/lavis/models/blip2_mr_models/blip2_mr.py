@@ -308,6 +308,7 @@ class BLIP2_MR(BaseModel):
             seed=cfg.get("seed", None),  # None: the engine's dropout stream follows torch's seed = run.seed + rank (train.py setup_seeds)
         )
         model.generate_device_search = bool(cfg.get("generate_device_search", False))
+        model.generate_device_sample = bool(cfg.get("generate_device_sample", False))
         model.generate_fused_decode = bool(cfg.get("generate_fused_decode", False))
         model.generate_graph_decode = bool(cfg.get("generate_graph_decode", False))
         model.load_checkpoint_from_config(cfg)
@@ -349,6 +350,11 @@ class BLIP2_MR(BaseModel):
     # decoding step.  Opt-in (model config key of the same name); taken for beam searches of <= 16 beams with both caches on and
     # max_length < 128, every other call runs the host search as before.
     generate_device_search = False
+    # sampling (use_nucleus_sampling) and one-beam greedy decoding with a repetition penalty with their state in device memory
+    # (mrblip.search.DeviceSampleSearch): no .cpu() of the [rows, vocab] logits, no host sort and no upload per decoding step.  Opt-in
+    # (model config key of the same name); taken with both caches on, max_length < 128, temperature > 0 and at most 256 rows, every other
+    # call runs the host sampler as before.  Independent of generate_device_search; the captured decode graph is not used on this route.
+    generate_device_sample = False
     # the self-attention block of every incremental decode step as one launch per layer (engine._t5_decode_step_fused, csrc/decode.hip):
     # host search, sampling and device search alike.  Opt-in (model config key of the same name).
     generate_fused_decode = False
@@ -592,6 +598,10 @@ class BLIP2_MR(BaseModel):
                     and self.generate_self_cache and int(max_length) < 128):
                 best = self._device_beam_search(B, K, int(max_length), int(min_length), float(length_penalty), float(repetition_penalty), n_ret,
                                                 cross, mask_k)
+            elif (self.generate_device_sample and (use_nucleus_sampling or greedy_pen) and cross is not None and self.generate_self_cache
+                  and int(max_length) < 128 and float(temperature) > 0 and B * K <= 256):
+                best = self._device_sample_search(B, n_ret, int(max_length), int(min_length), float(top_p), float(temperature),
+                                                  float(repetition_penalty), greedy_pen, cross, mask_k)
             elif cross is not None and self.generate_self_cache and int(max_length) < 128:
                 # incremental decoding (HF use_cache=True): one new position per step against the self-attention K/V cache, which the
                 # search re-orders through `parents` (HF's _reorder_cache)
@@ -666,7 +676,40 @@ class BLIP2_MR(BaseModel):
                                     "graph_captures": eng.dec_graph_captures - captures, "graph_replays": eng.dec_graph_replays - replays}
         return best
 
+    def _device_sample_search(self, B, n_ret, max_length, min_length, top_p, temperature, repetition_penalty, greedy, cross, mask):
+        """generate's sampling / penalised-greedy loop with the sampler on the device: every step is t5_decode_step on the search's device
+        tokens followed by search.step on the raw logits — the host only enqueues.  Rows never re-order, so there are no parents and the
+        self-attention cache stays in place.  Early stop and the one blocking transfer as in _device_beam_search.  The draws are keyed by
+        one 32-bit seed per call, taken on the host from ``sampling_generator`` (torch's default generator without one): a seeded
+        generator gives a reproducible series of calls."""
+        from mrblip.search import DeviceSampleSearch
+        eng = self.engine
+        seed = 0 if greedy else int(torch.randint(0, 2 ** 32, (1,), generator=getattr(self, "sampling_generator", None), dtype=torch.int64))
+        key = (B, n_ret, max_length, min_length, top_p, temperature, repetition_penalty, greedy)
+        search = self._dev_sample[1] if self._dev_sample is not None and self._dev_sample[0] == key else None
+        if search is None:   # (state lives in the engine's named workspaces: one search object at a time)
+            search = DeviceSampleSearch(B, n_ret, max_length, min_length=min_length, top_p=top_p, temperature=temperature,
+                                        repetition_penalty=repetition_penalty, eos_id=1, pad_id=0, start_id=0, greedy=greedy, seed=seed,
+                                        device=eng.dev, buf=eng.buf)
+            self._dev_sample = (key, search)
+        else:
+            search.reset(seed=seed)
+        state = eng.t5_decode_begin(search.R, max_length + 1)
+        if self.generate_fused_decode:
+            state["fused"] = True
+        for _ in range(max_length):
+            if self.generate_poll_done and search.finished():
+                break
+            logits = eng.t5_decode_step(state, search.tokens, None, cross, B, mask)
+            search.step(logits)
+            search.done_count_async()
+        best = search.finalize()
+        self.last_generate_stats = {"steps": search.steps, "steps_after_done": search.steps_after_done(), "search_host_s": search.host_seconds,
+                                    "graph_captures": 0, "graph_replays": 0}
+        return best
+
     _dev_search = None
+    _dev_sample = None
 
     # ------------------------------------------------------------------ checkpoints: trainable tensors only, reference key names
     def state_dict(self, *args, **kwargs):

@@ -123,6 +123,10 @@ _qf_layer_fwd = _sig("mrblip_qformer_layer_fwd", C.POINTER(QformerLayer), vp)
 _beam_topk = _sig("mrblip_beam_topk", vp, ll, vp, vp, ll, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, ll, vp)
 _beam_advance = _sig("mrblip_beam_advance", vp, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp)
 _beam_finalize = _sig("mrblip_beam_finalize", vp, ll, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp)
+_sample_topk = _sig("mrblip_sample_topk", vp, ll, vp, ll, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, ll, vp)
+_sample_advance = _sig("mrblip_sample_advance", vp, vp, vp, ll, vp, vp, vp, vp, vp, u32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp)
+_lib.mrblip_sample_topk_workspace_bytes.argtypes = [i32, i32, i32]
+_lib.mrblip_sample_topk_workspace_bytes.restype = ll
 _kv_gather_rows = _sig("mrblip_kv_gather_rows", vp, vp, vp, i32, i32, i32, i32, i32, vp)
 _decode_self_attn = _sig("mrblip_decode_self_attention", vp, vp, vp, ll, vp, ll, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp)
 _crop_resize_u8 = _sig("mrblip_crop_resize_u8", vp, i32, i32, i32, C.POINTER(C.c_int), i32, i32, vp, i32, vp)
@@ -143,6 +147,7 @@ EXPORTS = [
     "mrblip_qformer_layer_fwd", "mrblip_layernorm_bwd_cast",
     "mrblip_gemm_f16", "mrblip_layernorm_fwd_f16", "mrblip_attention_fwd_rowv_f16", "mrblip_patchify_f16", "mrblip_patchify_u8_f16",
     "mrblip_beam_topk", "mrblip_beam_advance", "mrblip_beam_finalize", "mrblip_kv_gather_rows",
+    "mrblip_sample_topk_workspace_bytes", "mrblip_sample_topk", "mrblip_sample_advance",
     "mrblip_crop_resize_u8", "mrblip_decode_self_attention",
     "mrblip_grad_stats_workspace_bytes", "mrblip_grad_sumsq", "mrblip_optim_prepare",
 ]
@@ -953,6 +958,62 @@ def kv_gather_rows(src, dst, parents, t: int):
     R, Lmax, inner = src.shape[-3:]
     assert parents.numel() == R
     _chk(_kv_gather_rows(_p(src), _p(dst), _p(parents), src.numel() // (R * Lmax * inner), R, Lmax, inner, int(t), _stream()))
+
+
+# ---- device-resident sampler (csrc/search.hip; driven by mrblip.search.DeviceSampleSearch)
+SAMPLE_MAX_K = 64     # candidates per row; also the row stride of cand_score / cand_index
+SAMPLE_MAX_ROWS = 256
+
+
+def sample_topk_workspace_bytes(R: int, top_k: int, V: int) -> int:
+    n = int(_lib.mrblip_sample_topk_workspace_bytes(int(R), int(top_k), int(V)))
+    if n < 0:
+        raise MrblipError(_lib.mrblip_last_error().decode())
+    return n
+
+
+def _req_cand(cand_score, cand_index, R, name):
+    _req(cand_score, torch.float32, name + ".cand_score")
+    _req(cand_index, torch.int32, name + ".cand_index")
+    for t in (cand_score, cand_index):
+        if t.dim() != 2 or tuple(t.shape) != (R, SAMPLE_MAX_K) or t.stride(0) != SAMPLE_MAX_K:
+            raise MrblipError(f"{name}: candidates are contiguous [R = {R}, {SAMPLE_MAX_K}] tensors, got {tuple(t.shape)} {t.stride()}")
+
+
+def sample_topk(logits, seqs, cur_len: int, top_k: int, cand_score, cand_index, ws, *, min_length: int = 1, eos_id: int = 1,
+                repetition_penalty: float = 1.0):
+    """cand_score / cand_index [R, 64] <- per row the k = min(top_k, V) best warped RAW logits (repetition penalty over seqs[:, :cur_len],
+    EOS -> -inf while cur_len < min_length), best first, equal scores by lower token id; slots k..63: -inf / -1.  logits fp32 [R, V];
+    seqs int32 [R, >= cur_len]; ws: uint8 scratch of sample_topk_workspace_bytes(R, top_k, V)."""
+    _req(logits, torch.float32, "sample_topk.logits")
+    _req(seqs, torch.int32, "sample_topk.seqs")
+    if logits.dim() != 2 or seqs.dim() != 2 or seqs.shape[0] != logits.shape[0]:
+        raise MrblipError(f"sample_topk: logits [R, V] and seqs [R, >= cur_len], got {tuple(logits.shape)} / {tuple(seqs.shape)}")
+    R, V = logits.shape
+    _req_cand(cand_score, cand_index, R, "sample_topk")
+    _chk(_sample_topk(_p(logits), _ld(logits), _p(seqs), _ld(seqs), R, V, int(cur_len), int(top_k), int(min_length), int(eos_id),
+                      float(repetition_penalty), _p(cand_score), _p(cand_index), _p(ws), ws.numel() * ws.element_size(), _stream()))
+
+
+def sample_advance(cand_score, cand_index, seq, tokens, unfinished, length, done_count, V: int, top_k: int, cur_len: int, *, top_p: float = 0.9,
+                   temperature: float = 1.0, greedy: bool = False, uniforms=None, seed: int = 0, eos_id: int = 1, pad_id: int = 0):
+    """one sampling (or greedy) step of every row on the candidates of sample_topk: draws the token (fp64 decisions, include/mrblip_hip.h),
+    writes it to seq[:, cur_len] and tokens, updates unfinished / length / done_count (all int32 on the device).  uniforms: fp32
+    [>= cur_len, R] draws in [0, 1) (row cur_len - 1 is used), or None for the built-in counter hash keyed by ``seed``."""
+    _req(seq, torch.int32, "sample_advance.seq")
+    R = seq.shape[0]
+    _req_cand(cand_score, cand_index, R, "sample_advance")
+    for t, n, name in ((tokens, R, "tokens"), (unfinished, R, "unfinished"), (length, R, "length"), (done_count, 1, "done_count")):
+        _req(t, torch.int32, "sample_advance." + name)
+        if t.numel() != n:
+            raise MrblipError(f"sample_advance.{name}: {n} int32 entries expected, got {tuple(t.shape)}")
+    if uniforms is not None:
+        _req(uniforms, torch.float32, "sample_advance.uniforms")
+        if not uniforms.is_contiguous() or uniforms.numel() < int(cur_len) * R:
+            raise MrblipError(f"sample_advance.uniforms: contiguous fp32 [>= {int(cur_len)}, {R}] expected, got {tuple(uniforms.shape)}")
+    _chk(_sample_advance(_p(cand_score), _p(cand_index), _p(seq), _ld(seq), _p(tokens), _p(unfinished), _p(length), _p(done_count), _p(uniforms),
+                         int(seed) & 0xFFFFFFFF, R, int(V), int(top_k), int(cur_len), int(eos_id), int(pad_id), float(temperature), float(top_p),
+                         1 if greedy else 0, _stream()))
 
 
 # ---- fused cached self-attention of generate's decode step (csrc/decode.hip)

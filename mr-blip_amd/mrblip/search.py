@@ -329,3 +329,145 @@ class DeviceBeamSearch:
         hyps = [out[b, r, 2:2 + int(out[b, r, 0])].to(torch.long) for b in range(self.B) for r in range(self.num_return)]
         self.host_seconds += time.perf_counter() - t0
         return hyps
+
+
+class DeviceSampleSearch:
+    """``sample_search`` with its whole state in device memory (csrc/search.hip): the warp of the raw logits, the top-k selection, the
+    top-p cut, the draw and the row bookkeeping run as HIP kernels, so a decoding loop never waits for the host:
+
+        search = DeviceSampleSearch(B, num_return, max_new, ..., seed=seed)
+        for _ in range(max_new):
+            if search.finished():                       # polls an event, never waits
+                break
+            logits = decoder(search.tokens)             # device int32 [R]: newest token of every row (rows never re-order)
+            search.step(logits)                         # RAW fp32 logits [R, V]
+            search.done_count_async()
+        seqs = search.finalize()                        # the one blocking transfer
+
+    The constructor mirrors ``sample_search``; ``finalize`` returns what it returns (R = batch * num_return sequences, item-major, start
+    token first, each trimmed after its first EOS).  greedy=True is HF's greedy decoding on penalised raw logits (no temperature, cut
+    or draw).  Decisions (include/mrblip_hip.h, mrblip_sample_advance): the k = min(top_k, V) best warped logits, higher first, EQUAL
+    logits by lower token id — HF's top-k keeps every tie with the k-th logit, the device keeps exactly k — then softmax at the
+    temperature, HF's top-p cut and one draw per row in fp64.  The draws come from a counter hash of (row, step, seed), or from
+    ``uniforms`` (fp32 [max_new_tokens, R] on the device, in [0, 1)) when the caller has a generator of its own.
+
+    State: ONE int32 block — seq [R, L] (L = max_new + 1, start token first), tokens [R], unfinished [R], length [R] (position after the
+    row's first EOS, 0 while it has none), done_count [1], cand_index [R, 64], cand_score [R, 64] (fp32 bits) — taken from ``buf`` (a
+    named-workspace allocator such as ``Engine.buf``) when given; a reset is one fill plus setting the unfinished flags."""
+
+    def __init__(self, batch: int, num_return: int, max_new_tokens: int, min_length: int = 1, top_p: float = 0.9, temperature: float = 1.0,
+                 repetition_penalty: float = 1.0, eos_id: int = 1, pad_id: int = 0, start_id: int = 0, greedy: bool = False, top_k: int = 50,
+                 seed: int = 0, device=None, buf=None, poll_lag: int = 2, uniforms: Optional[torch.Tensor] = None):
+        from mrblip import ops
+        self._ops = ops
+        R = int(batch) * max(1, int(num_return))
+        assert 1 <= R <= ops.SAMPLE_MAX_ROWS, f"DeviceSampleSearch: 1..{ops.SAMPLE_MAX_ROWS} rows"
+        assert 1 <= int(top_k) <= ops.SAMPLE_MAX_K, f"DeviceSampleSearch: top_k 1..{ops.SAMPLE_MAX_K} (0, HF's 'no top-k', keeps the host path)"
+        assert int(max_new_tokens) >= 1 and float(temperature) > 0 and float(top_p) > 0
+        self.B, self.R, self.max_new, self.L = int(batch), R, int(max_new_tokens), int(max_new_tokens) + 1
+        self.min_length, self.top_p, self.temperature = int(min_length), float(top_p), float(temperature)
+        self.repetition_penalty, self.greedy = float(repetition_penalty), bool(greedy)
+        self.top_k = 1 if self.greedy else int(top_k)            # (greedy: rank 0 is all the step needs)
+        self.eos_id, self.pad_id, self.start_id = int(eos_id), int(pad_id), int(start_id)
+        self.poll_lag, self.seed, self.uniforms = int(poll_lag), int(seed) & 0xFFFFFFFF, uniforms
+        self.device = torch.device(device if device is not None else "cuda")
+        self._buf = buf
+        L, NK = self.L, ops.SAMPLE_MAX_K
+        parts = [("seq", R * L), ("tokens", R), ("unfinished", R), ("length", R), ("done_count", 1), ("cand_index", R * NK), ("cand_score", R * NK)]
+        self._ints = self._alloc("ss_ints", sum(n for _, n in parts), torch.int32)
+        off = 0
+        for name, n in parts:
+            setattr(self, "_" + name, self._ints[off:off + n])
+            off += n
+        self._n_out = R * L + 3 * R                              # seq, tokens, unfinished, length: what finalize brings back
+        self._seq = self._seq.view(R, L)
+        self._cand_index = self._cand_index.view(R, NK)
+        self._cand_score = self._cand_score.view(torch.float32).view(R, NK)
+        self._ws = None
+        # early stop without blocking: the done counter of every step lands in a pinned slot of its own, behind an event
+        self._slots = torch.full((self.max_new,), -1, dtype=torch.int32).pin_memory()
+        self._events = [torch.cuda.Event() for _ in range(self.max_new)]
+        self.reset()
+
+    def _alloc(self, name, n, dtype):
+        if self._buf is not None:
+            return self._buf(name, (n,), dtype)
+        return torch.zeros(n, dtype=dtype, device=self.device)
+
+    def reset(self, seed: Optional[int] = None):
+        """back to the state before the first step (start token, every row unfinished); ``seed`` re-keys the draws.  Only enqueues."""
+        if seed is not None:
+            self.seed = int(seed) & 0xFFFFFFFF
+        self._ints.zero_()
+        self._unfinished.fill_(1)
+        if self.start_id != 0:
+            self._seq[:, 0].fill_(self.start_id)
+            self._tokens.fill_(self.start_id)
+        self._slots.fill_(-1)
+        self.cur_len, self.steps, self._recorded, self._finalized, self.host_seconds = 1, 0, 0, False, 0.0
+
+    @property
+    def tokens(self) -> torch.Tensor:
+        """the decoder's input for the next step: int32 [R] on the device"""
+        return self._tokens
+
+    @property
+    def sequences(self) -> torch.Tensor:
+        """int32 [R, cur_len] view of the running sequences (start token first)"""
+        return self._seq[:, :self.cur_len]
+
+    def step(self, logits_dev: torch.Tensor):
+        """raw fp32 next-token logits [R, V] of the current rows -> one new token per row; launches only"""
+        import time
+        t0 = time.perf_counter()
+        ops = self._ops
+        assert not self._finalized and self.steps < self.max_new, "DeviceSampleSearch.step: past max_new_tokens (or after finalize)"
+        R, V = logits_dev.shape
+        assert R == self.R
+        need = ops.sample_topk_workspace_bytes(R, self.top_k, V)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = self._alloc("ss_ws", need, torch.uint8)
+        ops.sample_topk(logits_dev, self._seq, self.cur_len, self.top_k, self._cand_score, self._cand_index, self._ws, min_length=self.min_length,
+                        eos_id=self.eos_id, repetition_penalty=self.repetition_penalty)
+        ops.sample_advance(self._cand_score, self._cand_index, self._seq, self._tokens, self._unfinished, self._length, self._done_count, V,
+                           self.top_k, self.cur_len, top_p=self.top_p, temperature=self.temperature, greedy=self.greedy, uniforms=self.uniforms,
+                           seed=self.seed, eos_id=self.eos_id, pad_id=self.pad_id)
+        self.steps += 1
+        self.cur_len += 1
+        self.host_seconds += time.perf_counter() - t0
+
+    def done_count_async(self):
+        """enqueue the copy of the done counter after the last step into that step's pinned slot, and record the step's event"""
+        i = self.steps - 1
+        assert i >= 0 and self._recorded == i, "done_count_async: once after every step"
+        self._slots[i:i + 1].copy_(self._done_count, non_blocking=True)
+        self._events[i].record()
+        self._recorded = i + 1
+
+    def finished(self) -> bool:
+        """True when the step ``poll_lag`` before the next one is known to have left every row finished (event QUERIED, never waited for)"""
+        i = self.steps - self.poll_lag
+        if i < 0 or i >= self._recorded or not self._events[i].query():
+            return False
+        return int(self._slots[i]) == self.R
+
+    def steps_after_done(self) -> int:
+        """after finalize: steps that were enqueued although every row was already finished (the price of not waiting)"""
+        assert self._finalized
+        for i in range(self._recorded):
+            if int(self._slots[i]) == self.R:
+                return self.steps - (i + 1)
+        return 0
+
+    def finalize(self) -> List[torch.Tensor]:
+        assert not self._finalized and self.steps >= 1
+        self._finalized = True
+        out = self._ints[:self._n_out].cpu()                     # the one blocking transfer: everything enqueued has run after it
+        import time
+        t0 = time.perf_counter()
+        R, L = self.R, self.L
+        seq, length = out[:R * L].view(R, L), out[R * L + 2 * R:].tolist()
+        # surplus steps after a row's EOS only appended pads: trimming removes them; a row without EOS keeps all cur_len tokens
+        seqs = [seq[r, :length[r] if length[r] > 0 else self.cur_len].to(torch.long) for r in range(R)]
+        self.host_seconds += time.perf_counter() - t0
+        return seqs
